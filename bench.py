@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - headline benchmark of the MI355X-native CF-NeRF ray-batch hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5|C1|W512|K64]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5|C1|W512|K64] [--full] [--dump-outputs DIR]
     N > 1: one rank per GPU.  Either the driver starts the ranks (python -m torch.distributed.run --nproc-per-node N
     bench.py --gpus N ...: WORLD_SIZE is set) or - plain `python bench.py --gpus N` - this process, which has not touched
     the GPU, starts them itself as a child torch.distributed.run and relays rank 0's JSON line.
@@ -17,11 +17,14 @@ A "step" is one pass of the hot path over one batch of synthetic rays of a BASEL
   K64   the reference's DEFAULT latent count (--K_samples 64, RUN:631): N_rand 1024, W 256 - train step
 S = 128 samples always (the reference's hard-coded table; single pass - it has no fine network).
   --mode train: forward + KDE-NLL loss + backward + Adam;  --mode eval: fused forward render only.
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure or check (rocprofv3 counter
+passes, per-stage kernel times, other precisions / configs, the eval and PSNR blocks, the CPU leg) runs only with --full.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy, before anything else runs.
 Rays are sharded across ranks (weak scaling: rays per GPU fixed); the only exchange is one RCCL all-reduce of the flat
 gradient per train step.  Prints ONE JSON line on rank 0.  At N > 1 the line explains itself: `comm` (exposed exchange time
 per step from two HIP events around the all-reduce on the compute stream, payload, the backend and world size torch.distributed
-reports), `rank_skew` (min / max over ranks of the step and forward-kernel times), `psnr` (the sharded ray pool + Trainer on the
-stand-in scene, with `vs_single_process`), `cpu_baseline` (rank 0).  Exit codes: 2 = fewer GPUs than --gpus, 3 = the process
+reports), `rank_skew` (min / max over ranks of the step and forward-kernel times) and, with --full, `psnr` (the sharded ray pool +
+Trainer on the stand-in scene, with `vs_single_process`), `cpu_baseline` (rank 0).  Exit codes: 2 = fewer GPUs than --gpus, 3 = the process
 group could not be initialised or does not span --gpus ranks.
 """
 import argparse
@@ -245,7 +248,8 @@ class Workload:
 
 def timed(wl, steps, warmup, sync, per_step=None):
     """W untimed steps, then exactly K steps between two (barrier + device sync) points.  `per_step` (a list) receives the
-    K step durations in ms from one HIP event per step on the launch stream (no host sync inside the region)."""
+    K step durations in ms from one HIP event per step on the launch stream (no host sync inside the region).  What the last
+    step returned is kept in `wl.last`."""
     for _ in range(warmup):
         wl.step()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] if per_step is not None else None
@@ -254,7 +258,7 @@ def timed(wl, steps, warmup, sync, per_step=None):
     if ev:
         ev[0].record()
     for i in range(steps):
-        wl.step()
+        wl.last = wl.step()
         if ev:
             ev[i + 1].record()
     sync()
@@ -262,6 +266,34 @@ def timed(wl, steps, warmup, sync, per_step=None):
     if ev:
         per_step.extend(ev[i].elapsed_time(ev[i + 1]) for i in range(steps))
     return dt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: what the timed path handed its caller in its LAST step, one DIR/<name>.npy per array (float32 / float64), so that
+    two builds run with the same arguments (same seeded inputs) can be compared output for output.  A train step returns the
+    scalars [loss, loss_nll, mse, psnr] and leaves the updated parameters, their gradient and the forward's per-latent maps in place;
+    an eval step returns the maps (C5: the fused K-statistics of the image rows)."""
+    ret = wl.last
+    if isinstance(ret, dict):
+        arrays = dict(ret)
+    elif wl.mode == "train":
+        tr = wl.trainer
+        arrays = {"scalars": ret, "params": wl.net.flat, "grad": tr.grad, "rgb_map": tr.rgb_map, "disp_map": tr.disp,
+                  "depth_map": tr.depth, "entropy": tr.entropy}
+    else:
+        rgb, disp, depth, extras = ret
+        arrays = {"rgb_map": rgb, "disp_map": disp, "depth_map": depth, **extras}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items() if torch.is_tensor(v)}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def launch_ranks(n, argv):
@@ -561,23 +593,30 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None, help="default: C2 (1024 rays per GPU, K=4) at every GPU count")
     ap.add_argument("--mode", choices=["train", "eval"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra measurements reported next to the main line (bf16x3, W512 stress row, "
-                                                          "PSNR block, coarse+fine extension, config 4 at N > 1)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: the rocprofv3 counter "
+                                                        "passes, per-stage kernel times, the extra measurements (see --no-alt) and the CPU leg "
+                                                        "(see --no-cpu-baseline).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; same arguments = same inputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the PSNR agreement checks")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the extra measurements reported next to the main line (bf16x3, "
+                                                          "W512 stress row, sliced batch, eval block, PSNR block, coarse+fine extension, "
+                                                          "config 4 at N > 1)")
     ap.add_argument("--precision", choices=["fp32", "bf16x3"], default="fp32",
                     help="fp32 = exact-fp32 MFMA (default, the measured parity path); bf16x3 = opt-in split-bf16 MFMA mode")
     ap.add_argument("--psnr-steps", type=int, default=2000, help="train steps of the PSNR block (procedural stand-in scene)")
     ap.add_argument("--extension", action="store_true", help="also time the coarse + fine sampling EXTENSION (`alt_config`; not in the reference, "
                                                              "parity unpinned - off by default since round 5: the default line carries `eval` instead)")
     args = ap.parse_args()
+    alt_on = args.full and not args.no_alt
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher above us: start the ranks ourselves (nothing in this process has touched the GPU yet)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
 
-    # counters of the dominant kernel observed by this very run (default one-GPU line only; child passes BEFORE the first GPU call here)
+    # counters of the dominant kernel observed by this very run (--full one-GPU C2 line only; child passes BEFORE the first GPU call here)
     live = None
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_alt and args.config is None and args.precision == "fp32"
+    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and alt_on and args.config is None and args.precision == "fp32"
             and os.environ.get("CFNERF_BENCH_LIVE_PMC", "1") != "0"):
         live = live_pmc(args.mode or "train")
 
@@ -635,6 +674,8 @@ def main():
 
     step_ms = []
     dt_own = timed(wl, args.steps, args.warmup, sync, step_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)      # before anything below steps the model again
     dt = max_over_ranks(dt_own)
     # duration of the dominant kernel: mean over the launches of the timed region, HIP events on the launch stream
     fwd_ms = wl.fwd_mean_ms(args.steps)
@@ -658,12 +699,12 @@ def main():
                     overlap_comm_pays_if="exposed_ms_mean > ~0.15 ms: the two-bucket form costs ~0.13 ms of gathers / scatters / a second "
                                          "launch per step (measured on one GPU) and can hide at most the early bucket's ~3/4 of the payload "
                                          "under the last ~0.2 ms of the backward (CFNERF_BENCH_OVERLAP=1 measures it)")
-    kms = wl.kernel_ms(sync)
-    extras = world == 1 and not args.no_alt and name == "C2" and args.precision == "fp32" and mode == "train"
+    kms = wl.kernel_ms(sync) if args.full else None
+    extras = world == 1 and alt_on and name == "C2" and args.precision == "fp32" and mode == "train"
 
     # the opt-in split-bf16 mode, measured the same way right after (every rank runs it: the all-reduce is inside)
     alt = None
-    if args.precision == "fp32" and not args.no_alt and name != "C5":
+    if args.precision == "fp32" and alt_on and name != "C5":
         wl.net.set_precision("bf16x3")
         dta = max_over_ranks(timed(wl, args.steps, min(3, args.warmup) or 1, sync))
         alt_fwd_ms = wl.fwd_mean_ms(args.steps)
@@ -682,9 +723,9 @@ def main():
                                    "would give 0.40, the remaining candidates sum to 0.42-0.45 (profiles/r03_pmc_summary.txt section pmc_b16, "
                                    "profiles/EXPERIMENTS.md, round 3)"}
 
-    # BASELINE config 4 (K = 16, 1024 rays per GPU) next to the line when the job spans several GPUs (default run only)
+    # BASELINE config 4 (K = 16, 1024 rays per GPU) next to the line when the job spans several GPUs (--full default-config run only)
     cfg4 = None
-    if world > 1 and not args.no_alt and args.config is None and args.precision == "fp32" and mode == "train":
+    if world > 1 and alt_on and args.config is None and args.precision == "fp32" and mode == "train":
         wl.__dict__.pop("trainer", None)
         wl.net.release_workspace()
         w4 = Workload("C4", "train", rank, world, dev, "fp32", force_dist)
@@ -696,7 +737,7 @@ def main():
         w4.net.release_workspace()
         del w4
 
-    # SURVEY 8d "stress row": the authors' own recipe, next to the headline line (one GPU, default train run only)
+    # SURVEY 8d "stress row": the authors' own recipe, next to the headline line (one GPU, --full default train run only)
     stress = None
     if extras:
         wl.__dict__.pop("trainer", None)
@@ -761,12 +802,12 @@ def main():
         del wh
 
     # The OTHER half of SURVEY 8(d)'s metric, "rays/sec of eval render" (the reference's render_path_train / uncertainty maps, RUN:247-314,
-    # 1117-1131), in the default line at every GPU count, after the timed region: the C2 batch in eval mode (perturb off, fixed latents
+    # 1117-1131), in the --full line at every GPU count, after the timed region: the C2 batch in eval mode (perturb off, fixed latents
     # with the last one zeroed: one fused forward launch per step, rays per GPU fixed) and BASELINE config 5 - one 800 x 800 image at
     # K = 32 with the K-statistics (mean / uncertainty / disparity / depth) reduced inside the kernel, rows tiled across the ranks
     # with no exchange.  Both timed like the headline: barrier + device sync on both sides, max over ranks.
     evalb = None
-    if not args.no_alt and name == "C2" and args.precision == "fp32" and mode == "train" and not force_dist:
+    if alt_on and name == "C2" and args.precision == "fp32" and mode == "train" and not force_dist:
         try:                                   # (like the PSNR block: nothing here may take the headline line down with it - ADVICE r5)
             wl.__dict__.pop("trainer", None)
             wl.net.release_workspace()
@@ -800,11 +841,11 @@ def main():
                 raise                          # a rank that fell out of max_over_ranks cannot be papered over
             evalb = dict(evalb or {}, error=f"{type(e).__name__}: {e}")
 
-    # PSNR, the second half of the headline metric, on the synthetic stand-in scene - at EVERY GPU count (default train run only): one rank
+    # PSNR, the second half of the headline metric, on the synthetic stand-in scene - at EVERY GPU count (--full default train run only): one rank
     # trains 1024-ray batches, N ranks train world x 1024-ray global batches through the sharded ray pool + the Trainer's all-reduce.
     # Nothing here may take the headline line down with it: a failure is reported inside the psnr object.
     psnr = None
-    if not args.no_alt and name == "C2" and args.precision == "fp32" and mode == "train" and args.psnr_steps > 0 and not force_dist:
+    if alt_on and name == "C2" and args.precision == "fp32" and mode == "train" and args.psnr_steps > 0 and not force_dist:
         wl.__dict__.pop("trainer", None)
         wl.net.release_workspace()
         try:
@@ -862,7 +903,8 @@ def main():
         if same_gpu and world > 1:
             out["config"]["parallelism"] += " [CFNERF_BENCH_SAME_GPU=1: all ranks share cuda:0 and exchange over gloo - a code-path test, not a scaling number]"
         if mode == "train":
-            out["kernel_ms"] = kms
+            if kms is not None:
+                out["kernel_ms"] = kms
             out["step_frac_of_peak"] = 3 * fl * wl.launches_per_step() / (dt / args.steps) / 1e12 / FP32_MFMA_PEAK_TF
         if psnr is not None:
             out["psnr"] = psnr
@@ -899,7 +941,7 @@ def main():
     # the CPU leg - at every N, on rank 0, AFTER the final barrier (the other ranks are done; nothing waits in a collective while the host
     # cores are timed): the oracle as the CPU baseline and as the checker of the two PSNR agreements.  A failure in here is reported
     # inside the object it belongs to; the headline line is printed regardless.
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(mode, wl.cfg)
         except Exception as e:

@@ -1,7 +1,7 @@
 """-m gpu: bench.py keeps the driver's contract - ONE JSON line last on stdout with the agreed keys (metric / value / unit /
 n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the
-`roofline`, `cpu_baseline` and `psnr` objects, the numbers in it are consistent with each other, and `--gpus N` works both
-under a launcher and on its own.
+`roofline` object and, with `--full`, the `cpu_baseline` and `psnr` objects, the numbers in it are consistent with each other,
+`--dump-outputs` writes the last timed step's outputs, and `--gpus N` works both under a launcher and on its own.
 
 bench.py runs as __main__ inside a fresh child of the fork server tests/conftest.py starts at collection time, never as a
 fork+exec of this (possibly GPU-initialised) pytest process."""
@@ -9,6 +9,7 @@ import json
 import os
 import tempfile
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def run_bench(*args, env=None, timeout=900):
 
 
 def test_default_line_has_the_contract_keys_and_is_self_consistent():
-    d = run_bench("--steps", "6", "--warmup", "2", "--no-alt")
+    d = run_bench("--full", "--steps", "6", "--warmup", "2", "--no-alt")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline", "ms_per_step_median"):
         assert k in d, k
@@ -61,9 +62,30 @@ def test_default_line_has_the_contract_keys_and_is_self_consistent():
     assert d["value"] > 50 * c["value"]
 
 
+def test_plain_line_times_only_the_steps_and_dumps_their_outputs(tmp_path):
+    """Without --full the line is the headline alone (nothing measured outside the timed steps), --steps sets the timed steps, and
+    --dump-outputs writes what the last timed step computed: the same arguments give the same seeded inputs, so two runs agree."""
+    runs = []
+    for i in range(2):
+        d = run_bench("--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / str(i)))
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["config"]["workload"].startswith("C2") and d["dtype"] == "f32"
+        assert abs(d["value"] - 1024 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        for k in ("cpu_baseline", "psnr", "eval", "alt_precision", "stress_w512", "sliced_batch_n8192", "kernel_ms"):
+            assert k not in d, k
+        assert d["roofline"]["traffic_source"] != "live"
+        runs.append({f.name[:-4]: np.load(f) for f in (tmp_path / str(i)).glob("*.npy")})
+    a, b = runs
+    assert {"scalars", "params", "grad", "rgb_map"} <= set(a) and set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["scalars"].shape == (4,) and a["rgb_map"].shape == (1024, 3, 4)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-4, atol=1e-6, err_msg=k)
+
+
 def test_eval_mode_and_other_configs_run():
     # eval WITHOUT --no-alt: the train-only side measurements (stress row, extension, PSNR) must stay out of an eval line
-    d = run_bench("--mode", "eval", "--steps", "4", "--warmup", "1", "--no-cpu-baseline")
+    d = run_bench("--full", "--mode", "eval", "--steps", "4", "--warmup", "1", "--no-cpu-baseline")
     assert d["config"]["workload"].startswith("C2") and "eval" in d["config"]["workload"] and d["value"] > 0
     assert "stress_w512" not in d and "alt_config" not in d and "psnr" not in d and "kernel_ms" not in d
     d = run_bench("--config", "C4", "--steps", "3", "--warmup", "1", "--no-alt", "--no-cpu-baseline")
@@ -76,7 +98,7 @@ def test_default_line_observes_its_own_counters():
     import shutil
     if shutil.which("rocprofv3") is None:
         pytest.skip("no rocprofv3 on this box")
-    d = run_bench("--steps", "4", "--warmup", "1", "--psnr-steps", "0", "--no-cpu-baseline", env={"CFNERF_BENCH_LIVE_PMC": "1"})
+    d = run_bench("--full", "--steps", "4", "--warmup", "1", "--psnr-steps", "0", "--no-cpu-baseline", env={"CFNERF_BENCH_LIVE_PMC": "1"})
     r = d["roofline"]
     assert r["traffic_source"] == "live" and "OBSERVED BY THIS RUN" in r["traffic_unit"]
     # train forward: ~1.46 GB of stash written + ~0.1 GB read per launch; matrix pipe 75-90 % busy
@@ -86,7 +108,7 @@ def test_default_line_observes_its_own_counters():
 
 def test_psnr_block_is_in_the_default_line():
     """the second half of the headline metric: held-out PSNR on the synthetic stand-in scene, plus the HIP-vs-oracle agreement"""
-    d = run_bench("--steps", "4", "--warmup", "1", "--psnr-steps", "300")
+    d = run_bench("--full", "--steps", "4", "--warmup", "1", "--psnr-steps", "300")
     p = d["psnr"]
     assert "synthetic stand-in for LLFF-fern" in p["scene"] and p["unit"] == "dB" and p["steps"] == 300
     c = p["held_out_psnr_db_by_step"]
@@ -137,7 +159,7 @@ def test_gpus_2_default_line_explains_itself():
     """The N > 1 line carries the whole metric and its own diagnosis: `psnr` (sharded ray pool + Trainer on world x 1024-ray global
     batches, with the pass/fail `vs_single_process`), `comm` (exposed exchange time from two HIP events around the all-reduce, payload,
     the backend and world size torch.distributed reports), `rank_skew`, and `cpu_baseline` on rank 0.  Two ranks on cuda:0 over gloo."""
-    d = run_bench("--gpus", "2", "--steps", "4", "--warmup", "2", "--psnr-steps", "60", env={"CFNERF_BENCH_SAME_GPU": "1"}, timeout=1500)
+    d = run_bench("--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--psnr-steps", "60", env={"CFNERF_BENCH_SAME_GPU": "1"}, timeout=1500)
     assert d["n_gpus"] == 2 and d["config"]["workload"].startswith("C2")
     c = d["comm"]
     assert c["backend"] == "gloo" and c["world_size_reported"] == 2 and c["steps"] == 4
@@ -166,6 +188,6 @@ def test_gpus_2_default_line_explains_itself():
 
 def test_k64_config_runs():
     """the reference's default latent count (--K_samples 64, RUN:631) as a bench configuration"""
-    d = run_bench("--config", "K64", "--steps", "3", "--warmup", "1", "--no-alt", "--no-cpu-baseline")
+    d = run_bench("--full", "--config", "K64", "--steps", "3", "--warmup", "1", "--no-alt", "--no-cpu-baseline")
     assert d["config"]["workload"].startswith("K64") and "K=64" in d["config"]["workload"] and d["value"] > 0
     assert d["kernel_ms"]["bwd_tail"] > 0.1                                 # the tail kernel is K-proportional: ~0.34 ms at K = 64

@@ -4,8 +4,8 @@ set -uo pipefail
 : "${GRAFT_REPO_ROOT:?run this through gpurun}"
 R="$GRAFT_REPO_ROOT"; O="$R/gpurun_out"; T="${1:-r05}"; mkdir -p "$O"
 cd "$R"
-python bench.py > "$O/bench_${T}_default.json" 2> "$O/bench_${T}_default.err"
-B="--no-cpu-baseline --no-alt"
+python bench.py --full > "$O/bench_${T}_default.json" 2> "$O/bench_${T}_default.err"
+B="--full --no-cpu-baseline --no-alt"
 python bench.py $B --steps 50 > "$O/bench_${T}_c2.json" 2>> "$O/bench_${T}.err"
 python bench.py $B --steps 50 --mode eval > "$O/bench_${T}_eval.json" 2>> "$O/bench_${T}.err"
 python bench.py $B --steps 20 --config C3 > "$O/bench_${T}_c3.json" 2>> "$O/bench_${T}.err"
@@ -16,7 +16,7 @@ python bench.py $B --steps 3 --warmup 1 --config C5 > "$O/bench_${T}_c5.json" 2>
 python bench.py $B --steps 30 --config K64 > "$O/bench_${T}_k64.json" 2>> "$O/bench_${T}.err"
 python bench.py $B --steps 10 --warmup 3 --config N8192 > "$O/bench_${T}_n8192.json" 2>> "$O/bench_${T}.err"
 # the N > 1 line with everything in it (psnr + vs_single_process, comm, rank_skew, cpu_baseline): two ranks on ONE GPU over gloo, a code-path run
-CFNERF_BENCH_SAME_GPU=1 python bench.py --gpus 2 --steps 20 --psnr-steps 500 > "$O/bench_${T}_2ranks_same_gpu.json" 2>> "$O/bench_${T}.err"
+CFNERF_BENCH_SAME_GPU=1 python bench.py --full --gpus 2 --steps 20 --psnr-steps 500 > "$O/bench_${T}_2ranks_same_gpu.json" 2>> "$O/bench_${T}.err"
 for f in "$O"/bench_${T}_*.json; do python - "$f" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

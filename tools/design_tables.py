@@ -81,7 +81,7 @@ bt += f"| C5 (800 × 800, K 32 eval, fused uncertainty) | {num(c5['value'])} = {
 ap = D["alt_precision"]
 bt += f"| C2 bf16x3 (opt-in, `alt_precision`) | {num(ap['value'])} | {ap['ms_per_step']:.3f} | | | | | {ap['roofline']['frac']:.3f} of its 833 TF-equivalent |\n"
 cb, sb = D["cpu_baseline"], D["sliced_batch_n8192"]
-bt += (f"\nIn the default line too: `cpu_baseline` (the oracle on the host cores, the 1024-ray C2 step, thread count swept) {cb['value']:.0f} rays/s at {cb['cores']} threads; "
+bt += (f"\nIn the `--full` line too: `cpu_baseline` (the oracle on the host cores, the 1024-ray C2 step, thread count swept) {cb['value']:.0f} rays/s at {cb['cores']} threads; "
        f"`roofline.traffic` observed by the run {D['roofline']['traffic'] / 1e9:.3f} GB per forward launch (1.46 GB of it the stash; algorithmic ≈ 3.1 MB), PMC MFMA-busy "
        f"{D['roofline']['mfma_busy_frac_pmc']:.3f}; `sliced_batch_n8192` {num(sb['value'])} rays/s on a {sb['workspace_bytes'] / 2 ** 30:.2f} GiB workspace; "
        f"`psnr` {D['psnr']['value']:.1f} dB after {D['psnr']['steps']} steps ({D['psnr']['wall_s_incl_eval']:.1f} s incl. the evaluations), held-out PSNR within "
