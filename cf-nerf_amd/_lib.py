@@ -68,20 +68,25 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} is missing: build it with `python cf-nerf_amd/build.py` (needs hipcc). "
                 "The CF-NeRF hot path has no CPU or PyTorch fallback.")
-        if os.environ.get("CFNERF_LIB"):
+        override = bool(os.environ.get("CFNERF_LIB"))
+        if override:
             import sys
             print(f"cf-nerf_amd: warning: CFNERF_LIB is set - loading {LIB_PATH} instead of the in-tree libcfnerf_hip.so "
                   "(development aid for same-box A/B runs of two builds)", file=sys.stderr, flush=True)
         l = C.CDLL(LIB_PATH)
+        skipped = []
         for name, (res, args) in _SIGS.items():
             try:
                 fn = getattr(l, name)  # AttributeError here = header / library out of sync
             except AttributeError:
-                if os.environ.get("CFNERF_LIB"):
-                    continue           # (an OLDER build under the A/B override: entry points added since are simply absent there)
+                if override:
+                    skipped.append(name)   # (an OLDER build under the A/B override: entry points added since are simply absent there)
+                    continue
                 raise
             fn.restype = res
             fn.argtypes = args
+        if skipped:
+            print("cf-nerf_amd: warning: entry points absent from the CFNERF_LIB build: " + ", ".join(skipped), file=sys.stderr, flush=True)
         _lib = l
     return _lib
 

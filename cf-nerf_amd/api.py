@@ -93,16 +93,38 @@ def _device_of(*ts, default=None):
     return torch.device("cuda", torch.cuda.current_device()) if default is None else default
 
 
+def _pack_rays(H, W, focal, c2w=None, rays=None, n=None, pixel0=0, ndc=False, near=0., far=1., out=None, device=None):
+    """The packed ray batch every launch reads, ``[n, 11]`` = o3, d3, near, far, viewdir3 (RUN:504-507), on
+    ``cfnerf_rays_setup``: from a pose (pixels ``pixel0 .. pixel0 + n`` of the H x W image, default all of it) or from
+    explicit ``rays=(rays_o, rays_d)``.  ``near`` / ``far`` are numbers or per-ray tensors.  Written into ``out`` when given
+    (a persistent [n, 11] buffer), else into a new tensor on ``device`` (rays mode: the rays' device)."""
+    if c2w is not None:
+        arr, _keep = _pose_arg(c2w)
+        ro = rd = None
+        n = int(H) * int(W) if n is None else n
+    else:
+        arr = None
+        ro, rd = _f32c(rays[0].reshape(-1, 3)), _f32c(rays[1].reshape(-1, 3))
+        n, device = rd.shape[0], rd.device
+    if out is None:
+        out = torch.empty(n, 11, device=device)
+    nf, ff = (near if not torch.is_tensor(near) else 0.), (far if not torch.is_tensor(far) else 1.)
+    L.check(L.lib().cfnerf_rays_setup(int(H), int(W), float(focal), arr, L.ptr(ro), L.ptr(rd), n, pixel0, int(bool(ndc)), float(nf), float(ff),
+                                      L.ptr(out), L.stream()), "cfnerf_rays_setup")
+    if torch.is_tensor(near):
+        out[:, 6] = near.reshape(-1).to(out)
+    if torch.is_tensor(far):
+        out[:, 7] = far.reshape(-1).to(out)
+    return out
+
+
 def get_rays(H, W, focal, c2w):
     """HLP:288-297 on the ray set-up kernel: ``rays_o, rays_d [H,W,3]`` on the GPU (of ``c2w`` if it lives on one, else the
     current device)."""
     H, W = int(H), int(W)
     dev = _device_of(c2w)
-    arr, keep = _pose_arg(c2w)
-    packed = torch.empty(H * W, 11, device=dev)
     with torch.cuda.device(dev):
-        L.check(L.lib().cfnerf_rays_setup(H, W, float(focal), arr, None, None, H * W, 0, 0, 0.0, 1.0, L.ptr(packed), L.stream()),
-                "cfnerf_rays_setup")
+        packed = _pack_rays(H, W, focal, c2w=c2w, device=dev)
     return packed[:, 0:3].reshape(H, W, 3), packed[:, 3:6].reshape(H, W, 3)
 
 
@@ -178,7 +200,6 @@ def _shape_of(key: str, numel: int, cfg: L.Cfg):
 
 
 # --------------------------------------------------------------------------------------------
-@torch.no_grad()
 def flow_buffers(n_flows, device="cpu"):
     """The registered buffers of the reference's two flow stacks (MOD:323-333, FLW:180-181), which its ``state_dict()`` carries next to
     the parameters: key -> tensor.  Device-free host logic (a checkpoint this build writes holds exactly the reference's key set:
@@ -193,6 +214,7 @@ def flow_buffers(n_flows, device="cpu"):
     return out
 
 
+@torch.no_grad()
 def reference_init(shapes, netdepth, K_samples=None):
     """Initial values exactly as ``NeRF_Flows.__init__`` produces them under the same ``torch.manual_seed``
     (MOD:38-67, 339-350).  Throw-away CPU ``nn.Linear``s are created in the reference's construction order, so torch's
@@ -230,6 +252,13 @@ def reference_init(shapes, netdepth, K_samples=None):
     if missing:
         raise RuntimeError(f"reference_init: no rule for {sorted(missing)}")
     return vals, latents
+
+
+def _latents(model, eps_alpha, eps_rgb, train, device):
+    """[K,4] latents of a launch: the explicit ``eps_rgb | eps_alpha`` when given, else fresh train draws or the fixed eval ones."""
+    if eps_alpha is not None or eps_rgb is not None:
+        return torch.cat([eps_rgb, eps_alpha], -1).to(device, torch.float32).contiguous()
+    return model.draw_eps() if train else model.eval_eps()
 
 
 class NeRF_Flows(nn.Module):
@@ -429,22 +458,16 @@ class NeRF_Flows(nn.Module):
         self._sync()
         xf = _f32c(x.reshape(-1, x.shape[-1]))
         P, K = xf.shape[0], self.K_samples
-        if eps_alpha is not None or eps_rgb is not None:
-            eps = torch.cat([eps_rgb, eps_alpha], -1).to(self.device, torch.float32).contiguous()
-        elif self._next_eps is not None:                            # latents chosen by the enclosing render_rays call
-            eps = self._next_eps
+        if self._next_eps is not None and eps_alpha is None and eps_rgb is None:
+            eps = self._next_eps                                    # latents chosen by the enclosing render_rays call
         else:
-            eps = self.eval_eps() if is_test else self.draw_eps()
+            eps = _latents(self, eps_alpha, eps_rgb, not is_test, self.device)
         if torch.is_grad_enabled() and self.flat.requires_grad and not is_test and P > 0:
             # the reference's forward is an autograd graph (MOD:188-291): so is this one - cfnerf_network_fwd with the
             # activation stash, differentiated by cfnerf_network_bwd (gradients reach the parameters; x is a constant)
             raw, ent = _NetworkFn.apply(self.flat, self, xf, eps)
             return raw, ent.reshape(1, 1, 1).expand(P, K, 1)         # MOD:291
-        raw = torch.empty(P, K, 4, device=self.device, dtype=torch.float32)
-        ent = torch.zeros(1, device=self.device, dtype=torch.float32)
-        flags = 0 if is_test else L.F_TRAIN
-        L.check(L.lib().cfnerf_network_fwd(self._h, L.ptr(xf), L.ptr(eps), P, K, flags, L.ptr(raw), L.ptr(ent), L.stream()),
-                "cfnerf_network_fwd")
+        raw, ent = _network_fwd(self, xf, eps, K, 0 if is_test else L.F_TRAIN)
         if is_test:
             return raw, torch.zeros_like(raw)                        # MOD:223
         return raw, ent.reshape(1, 1, 1).expand(P, K, 1)             # MOD:291
@@ -480,6 +503,15 @@ def _refuse_changed_params(model, token, pack_serial):
                            "optimizer.step() / Trainer.step() / load_state_dict())")
 
 
+def _network_fwd(model, xf, eps, K, flags):
+    """cfnerf_network_fwd of the encoded points ``xf [P,90]`` into new ``raw [P,K,4]`` and a zeroed entropy accumulator ``[1]``."""
+    raw = torch.empty(xf.shape[0], K, 4, device=xf.device)
+    ent = torch.zeros(1, device=xf.device)
+    L.check(L.lib().cfnerf_network_fwd(model.handle, L.ptr(xf), L.ptr(eps), xf.shape[0], K, flags, L.ptr(raw), L.ptr(ent), L.stream()),
+            "cfnerf_network_fwd")
+    return raw, ent
+
+
 class _NetworkFn(torch.autograd.Function):
     """NeRF_Flows.forward as an autograd node: cfnerf_network_fwd with the activation stash + cfnerf_network_bwd.  The model has
     ONE stash.  If a later grad-enabled forward replaced it before this node's backward runs (several chunks of one batch through
@@ -487,20 +519,14 @@ class _NetworkFn(torch.autograd.Function):
     have changed in between) and then differentiates: chunked callers train, at the price of one extra forward per chunk."""
 
     @staticmethod
-    def _forward_stash(model, xf, eps, raw, ent):
-        P, K = xf.shape[0], eps.shape[0]
-        model.ensure_workspace(1, P, K)
-        lib = L.lib()
-        L.check(lib.cfnerf_network_fwd(model.handle, L.ptr(xf), L.ptr(eps), P, K, L.F_TRAIN | L.F_STASH, L.ptr(raw), L.ptr(ent), L.stream()),
-                "cfnerf_network_fwd")
-        return lib.cfnerf_model_stash_generation(model.handle)
+    def _forward_stash(model, xf, eps):
+        model.ensure_workspace(1, xf.shape[0], eps.shape[0])
+        raw, ent = _network_fwd(model, xf, eps, eps.shape[0], L.F_TRAIN | L.F_STASH)
+        return raw, ent, L.lib().cfnerf_model_stash_generation(model.handle)
 
     @staticmethod
     def forward(ctx, flat, model, xf, eps):
-        P, K = xf.shape[0], eps.shape[0]
-        raw = torch.empty(P, K, 4, device=xf.device)
-        ent = torch.zeros(1, device=xf.device)
-        ctx.generation = _NetworkFn._forward_stash(model, xf, eps, raw, ent)
+        raw, ent, ctx.generation = _NetworkFn._forward_stash(model, xf, eps)
         ctx.model, ctx.xf, ctx.eps, ctx.n_params = model, xf, eps, flat.numel()
         ctx.params_at = _params_token(model)                       # the weights this graph was taken at
         ctx.pack_serial = model.pack_serial                        # ... and the packed copy of them the library held
@@ -517,9 +543,7 @@ class _NetworkFn(torch.autograd.Function):
             # the stash is gone (a later grad-enabled forward replaced it): re-run the forward - the SAME forward, the parameters being the
             # ones it was taken at (checked above; a re-pack of unchanged parameters in between is harmless here)
             model._sync()
-            P, K = ctx.xf.shape[0], ctx.eps.shape[0]
-            ctx.generation = _NetworkFn._forward_stash(model, ctx.xf, ctx.eps, torch.empty(P, K, 4, device=ctx.xf.device),
-                                                       torch.zeros(1, device=ctx.xf.device))
+            ctx.generation = _NetworkFn._forward_stash(model, ctx.xf, ctx.eps)[2]
         grad = torch.empty(ctx.n_params, device=model.flat.device)
         dr = _f32c(d_raw) if d_raw is not None else None
         de = _f32c(d_ent.reshape(1)) if d_ent is not None else None
@@ -529,23 +553,28 @@ class _NetworkFn(torch.autograd.Function):
         return grad, None, None, None
 
 
+def _composite_fwd(raw, z_vals, rays_d, white_bkgd):
+    """cfnerf_composite_fwd into new ``rgb_map [N,3,K], disp_map [N,K], weights [N,S,K], depth_map [N,K]`` (raw2outputs' order)."""
+    N, S, K = raw.shape[0], raw.shape[1], raw.shape[2]
+    dev = raw.device
+    rgb_map = torch.empty(N, 3, K, device=dev)
+    disp_map = torch.empty(N, K, device=dev)
+    depth_map = torch.empty(N, K, device=dev)
+    weights = torch.empty(N, S, K, device=dev)
+    L.check(L.lib().cfnerf_composite_fwd(L.ptr(raw), L.ptr(z_vals), L.ptr(rays_d), N, S, K, int(bool(white_bkgd)), L.ptr(rgb_map),
+                                         L.ptr(disp_map), L.ptr(depth_map), L.ptr(weights), L.stream()), "cfnerf_composite_fwd")
+    return rgb_map, disp_map, weights, depth_map
+
+
 class _CompositeFn(torch.autograd.Function):
     """raw2outputs (RUN:411-454) as an autograd node: cfnerf_composite_fwd + cfnerf_composite_bwd (stateless; differentiable with
     respect to raw through every output: rgb_map, disp_map, weights, depth_map)."""
 
     @staticmethod
     def forward(ctx, raw, z_vals, rays_d, white_bkgd):
-        N, S, K = raw.shape[0], raw.shape[1], raw.shape[2]
-        dev = raw.device
-        rgb_map = torch.empty(N, 3, K, device=dev)
-        disp_map = torch.empty(N, K, device=dev)
-        depth_map = torch.empty(N, K, device=dev)
-        weights = torch.empty(N, S, K, device=dev)
-        L.check(L.lib().cfnerf_composite_fwd(L.ptr(raw), L.ptr(z_vals), L.ptr(rays_d), N, S, K, int(bool(white_bkgd)), L.ptr(rgb_map),
-                                             L.ptr(disp_map), L.ptr(depth_map), L.ptr(weights), L.stream()), "cfnerf_composite_fwd")
         ctx.save_for_backward(raw, z_vals, rays_d)
         ctx.white_bkgd = int(bool(white_bkgd))
-        return rgb_map, disp_map, weights, depth_map
+        return _composite_fwd(raw, z_vals, rays_d, white_bkgd)
 
     @staticmethod
     def backward(ctx, d_rgb, d_disp, d_weights, d_depth):
@@ -618,23 +647,31 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
     """RUN:411-454 on the standalone composite kernel.  ``raw_noise_std`` is accepted and has no effect,
     exactly like the reference (the noise is generated but never added, RUN:432-442)."""
     _need_gpu(raw, "raw")
-    N, S, K = raw.shape[0], raw.shape[1], raw.shape[2]
     if torch.is_grad_enabled() and raw.requires_grad:                # differentiable like the reference's (with respect to raw)
         rc = raw.to(torch.float32).contiguous()
         return _CompositeFn.apply(rc, _f32c(z_vals), _f32c(rays_d), bool(white_bkgd))
-    raw_c, z_c, d_c = _f32c(raw), _f32c(z_vals), _f32c(rays_d)
-    dev = raw.device
-    rgb_map = torch.empty(N, 3, K, device=dev)
-    disp_map = torch.empty(N, K, device=dev)
-    depth_map = torch.empty(N, K, device=dev)
-    weights = torch.empty(N, S, K, device=dev)
-    L.check(L.lib().cfnerf_composite_fwd(L.ptr(raw_c), L.ptr(z_c), L.ptr(d_c), N, S, K, int(bool(white_bkgd)),
-                                         L.ptr(rgb_map), L.ptr(disp_map), L.ptr(depth_map), L.ptr(weights), L.stream()),
-            "cfnerf_composite_fwd")
-    return rgb_map, disp_map, weights, depth_map
+    return _composite_fwd(_f32c(raw), _f32c(z_vals), _f32c(rays_d), white_bkgd)
 
 
 # --------------------------------------------------------------------------------------------
+def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True, raw=False, weights=False, pts=False, kstats=False,
+                entropy=True):
+    """cfnerf_render_fwd of the packed ``rays [N,11]`` into newly allocated outputs.  Returns a dict with ``rgb_map [N,3,K]``,
+    ``disp_map`` / ``depth_map [N,K]`` (``maps``), ``raw [N,S,K,4]``, ``weights [N,S,K]``, ``pts [N,S,3]``, ``kstats [N,8]`` and the
+    zeroed accumulator ``entropy [1]``; an output that was not asked for is None.  S is that of ``z_vals [N,S]`` (explicit depths,
+    which the library then prefers to ``t_rand``) or of the sample table ``t_vals``."""
+    N, K = rays.shape[0], eps.shape[0]
+    S = z_vals.shape[1] if z_vals is not None else t_vals.shape[0]
+    dev = rays.device
+    new = lambda want, *shape: torch.empty(*shape, device=dev) if want else None
+    o = {'rgb_map': new(maps, N, 3, K), 'disp_map': new(maps, N, K), 'depth_map': new(maps, N, K), 'raw': new(raw, N, S, K, 4),
+         'weights': new(weights, N, S, K), 'pts': new(pts, N, S, 3), 'kstats': new(kstats, N, 8),
+         'entropy': torch.zeros(1, device=dev) if entropy else None}
+    L.check(L.lib().cfnerf_render_fwd(model.handle, L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), L.ptr(z_vals), L.ptr(eps), N, S, K, flags,
+                                      *(L.ptr(t) for t in o.values()), L.stream()), "cfnerf_render_fwd")
+    return o
+
+
 class _RenderFn(torch.autograd.Function):
     """Fused render (forward with activation stash) + cfnerf_render_bwd.  The model has ONE stash: the node remembers
     the generation of its forward and the backward is refused (loudly) if a later grad-enabled forward replaced it."""
@@ -642,29 +679,17 @@ class _RenderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flat, model, rays, t_vals, t_rand, eps, flags, want_pts, z_vals):
         N, K = rays.shape[0], eps.shape[0]
-        S = z_vals.shape[1] if z_vals is not None else t_vals.shape[0]
-        dev = rays.device
-        rgb_map = torch.empty(N, 3, K, device=dev)
-        disp = torch.empty(N, K, device=dev)
-        depth = torch.empty(N, K, device=dev)
-        raw = torch.empty(N, S, K, 4, device=dev)
-        pts = torch.empty(N, S, 3, device=dev) if want_pts else None
-        ent = torch.zeros(1, device=dev)
-        lib = L.lib()
-        model.ensure_workspace(N, S, K)
-        L.check(lib.cfnerf_render_fwd(model.handle, L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), L.ptr(z_vals), L.ptr(eps), N, S, K,
-                                      flags | L.F_STASH, L.ptr(rgb_map), L.ptr(disp), L.ptr(depth), L.ptr(raw), None,
-                                      L.ptr(pts), None, L.ptr(ent), L.stream()), "cfnerf_render_fwd")
+        model.ensure_workspace(N, z_vals.shape[1] if z_vals is not None else t_vals.shape[0], K)
+        o = _render_fwd(model, rays, t_vals, t_rand, eps, flags | L.F_STASH, z_vals, raw=True, pts=want_pts)
         ctx.model = model
         ctx.n_params = flat.numel()
-        ctx.generation = lib.cfnerf_model_stash_generation(model.handle)
+        ctx.generation = L.lib().cfnerf_model_stash_generation(model.handle)
         ctx.params_at, ctx.pack_serial = _params_token(model), model.pack_serial
         ctx.shape = (N, 3, K)
-        ctx.mark_non_differentiable(disp, raw)
-        if pts is None:
-            pts = torch.empty(0, device=dev)
+        pts = o['pts'] if want_pts else torch.empty(0, device=rays.device)
+        # (torch keeps only the LAST mark_non_differentiable call's tensors: pts alone, as before; the backward ignores d_disp / d_raw)
         ctx.mark_non_differentiable(pts)
-        return rgb_map, disp, depth, ent.reshape(()), raw, pts
+        return o['rgb_map'], o['disp_map'], o['depth_map'], o['entropy'].reshape(()), o['raw'], pts
 
     @staticmethod
     def backward(ctx, d_rgb, d_disp, d_depth, d_ent, d_raw, d_pts):
@@ -718,10 +743,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
         t_rand = _f32c(t_rand.to(dev))
     else:
         t_rand = None
-    if eps_alpha is not None or eps_rgb is not None:
-        eps = torch.cat([eps_rgb, eps_alpha], -1).to(dev, torch.float32).contiguous()
-    else:
-        eps = model.draw_eps() if is_train else model.eval_eps()
+    eps = _latents(model, eps_alpha, eps_rgb, is_train, dev)
     flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_TRAIN if is_train else 0)
     model._sync()
 
@@ -734,23 +756,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
         return {'rgb_map': rgb_map, 'disp_map': disp, 'depth_map': depth, 'raw': raw,
                 'loss_entropy': ent.reshape(1, 1, 1).expand(N * S, K, 1), 'pts': pts}
 
-    rgb_map = torch.empty(N, 3, K, device=dev)
-    disp = torch.empty(N, K, device=dev)
-    depth = torch.empty(N, K, device=dev)
-    raw = torch.empty(N, S, K, 4, device=dev) if is_train else None
-    pts = torch.empty(N, S, 3, device=dev) if is_train else None
-    wts = torch.empty(N, S, K, device=dev) if retweights else None
-    ent = torch.zeros(1, device=dev)
-    L.check(L.lib().cfnerf_render_fwd(model.handle, L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), None, L.ptr(eps), N, S, K, flags,
-                                      L.ptr(rgb_map), L.ptr(disp), L.ptr(depth), L.ptr(raw), L.ptr(wts), L.ptr(pts), None, L.ptr(ent),
-                                      L.stream()), "cfnerf_render_fwd")
-    ret = {'rgb_map': rgb_map, 'disp_map': disp, 'depth_map': depth}
+    o = _render_fwd(model, rays, t_vals, t_rand, eps, flags, raw=is_train, weights=retweights, pts=is_train)
+    ret = {k: o[k] for k in ('rgb_map', 'disp_map', 'depth_map')}
     if is_train:
-        ret['raw'] = raw
-        ret['loss_entropy'] = ent.reshape(1, 1, 1).expand(N * S, K, 1)
-        ret['pts'] = pts
+        ret['raw'] = o['raw']
+        ret['loss_entropy'] = o['entropy'].reshape(1, 1, 1).expand(N * S, K, 1)
+        ret['pts'] = o['pts']
     if retweights:
-        ret['weights'] = wts
+        ret['weights'] = o['weights']
     return ret
 
 
@@ -773,36 +786,25 @@ def _render_rays_hierarchical(ray_batch, network_fn, N_samples, N_importance, is
     tr = None
     if perturb > 0.:
         tr = _f32c((torch.rand([N, S]) if t_rand is None else t_rand).to(dev))
-    if eps_alpha is not None or eps_rgb is not None:
-        eps = torch.cat([eps_rgb, eps_alpha], -1).to(dev, torch.float32).contiguous()
-    else:
-        eps = model.draw_eps() if is_train else model.eval_eps()
+    eps = _latents(model, eps_alpha, eps_rgb, is_train, dev)
     if u_fine is None:      # det=(perturb == 0.) in nerf-pytorch
         u_fine = torch.linspace(0., 1., steps=N_importance).expand(N, N_importance) if not perturb > 0. else torch.rand(N, N_importance)
     u = _f32c(u_fine.to(dev))
     flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_TRAIN if is_train else 0)
     model._sync()
-    lib = L.lib()
-
-    def launch(S_, z_in, want_w):
-        rgb, disp, depth = torch.empty(N, 3, K, device=dev), torch.empty(N, K, device=dev), torch.empty(N, K, device=dev)
-        wts = torch.empty(N, S_, K, device=dev) if want_w else None
-        ent = torch.zeros(1, device=dev)
-        L.check(lib.cfnerf_render_fwd(model.handle, L.ptr(rays), L.ptr(tv), L.ptr(tr) if z_in is None else None, L.ptr(z_in), L.ptr(eps),
-                                      N, S_, K, flags, L.ptr(rgb), L.ptr(disp), L.ptr(depth), None, L.ptr(wts), None, None, L.ptr(ent),
-                                      L.stream()), "cfnerf_render_fwd")
-        return rgb, disp, depth, wts, ent
     with torch.no_grad():
-        rgb0, disp0, depth0, w0, _ = launch(S, None, True)
+        c = _render_fwd(model, rays, tv, tr, eps, flags, weights=True)
         z_all = torch.empty(N, S + N_importance, device=dev)
-        L.check(lib.cfnerf_sample_pdf(L.ptr(rays), L.ptr(tv), L.ptr(tr), flags, L.ptr(w0), L.ptr(u), N, S, K, N_importance, L.ptr(z_all),
-                                      L.stream()), "cfnerf_sample_pdf")
+        L.check(L.lib().cfnerf_sample_pdf(L.ptr(rays), L.ptr(tv), L.ptr(tr), flags, L.ptr(c['weights']), L.ptr(u), N, S, K, N_importance,
+                                          L.ptr(z_all), L.stream()), "cfnerf_sample_pdf")
     if is_train and N > 0 and torch.is_grad_enabled() and model.flat.requires_grad:
         rgb, disp, depth, ent, _raw, _pts = _RenderFn.apply(model.flat, model, rays, tv, None, eps, flags, False, z_all)
         ent = ent.reshape(1)
     else:
-        rgb, disp, depth, _, ent = launch(S + N_importance, z_all, False)
-    ret = {'rgb_map': rgb, 'disp_map': disp, 'depth_map': depth, 'rgb0': rgb0, 'disp0': disp0, 'depth0': depth0, 'z_vals': z_all}
+        f = _render_fwd(model, rays, tv, None, eps, flags, z_all)
+        rgb, disp, depth, ent = f['rgb_map'], f['disp_map'], f['depth_map'], f['entropy']
+    ret = {'rgb_map': rgb, 'disp_map': disp, 'depth_map': depth, 'rgb0': c['rgb_map'], 'disp0': c['disp_map'], 'depth0': c['depth_map'],
+           'z_vals': z_all}
     if is_train:
         ret['loss_entropy'] = ent.reshape(1, 1, 1).expand(N * (S + N_importance), K, 1)
     return ret
@@ -847,38 +849,18 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     """
     if not use_viewdirs:
         raise ValueError("use_viewdirs=False is not supported (the reference's model cannot run it, SURVEY R8)")
-    lib = L.lib()
-    if c2w is not None:
+    if c2w is not None:                          # a host pose goes into the kernel arguments as it is: no device round trip
         dev = kwargs["network_fn"].module.device if hasattr(kwargs.get("network_fn"), "module") else _unwrap(kwargs["network_fn"]).device
         sh = (H, W, 3)
-        N = H * W
-        packed = torch.empty(N, 11, device=dev)
-        arr, _keep = _pose_arg(c2w)              # a host pose goes into the kernel arguments as it is: no device round trip
-        if c2w_staticcam is None:
-            L.check(lib.cfnerf_rays_setup(H, W, float(focal), arr, None, None, N, 0, int(bool(ndc)), float(near), float(far),
-                                          L.ptr(packed), L.stream()), "cfnerf_rays_setup")
-        else:   # RUN:139-141: view directions from c2w, geometry from the static camera
-            L.check(lib.cfnerf_rays_setup(H, W, float(focal), arr, None, None, N, 0, 0, float(near), float(far), L.ptr(packed),
-                                          L.stream()), "cfnerf_rays_setup")
+        packed = _pack_rays(H, W, focal, c2w=c2w, ndc=ndc and c2w_staticcam is None, near=near, far=far, device=dev)
+        if c2w_staticcam is not None:   # RUN:139-141: view directions from c2w, geometry from the static camera
             vd = packed[:, 8:11].clone()
-            arr2, _keep2 = _pose_arg(c2w_staticcam)
-            L.check(lib.cfnerf_rays_setup(H, W, float(focal), arr2, None, None, N, 0, int(bool(ndc)), float(near), float(far),
-                                          L.ptr(packed), L.stream()), "cfnerf_rays_setup")
+            _pack_rays(H, W, focal, c2w=c2w_staticcam, ndc=ndc, near=near, far=far, out=packed)
             packed[:, 8:11] = vd
     else:
-        rays_o, rays_d = rays
-        _need_gpu(rays_d, "rays")
-        sh = tuple(rays_d.shape)
-        ro, rd = _f32c(rays_o.reshape(-1, 3)), _f32c(rays_d.reshape(-1, 3))
-        N = rd.shape[0]
-        packed = torch.empty(N, 11, device=rd.device)
-        nf, ff = (near if not torch.is_tensor(near) else 0.), (far if not torch.is_tensor(far) else 1.)
-        L.check(lib.cfnerf_rays_setup(H, W, float(focal), None, L.ptr(ro), L.ptr(rd), N, 0, int(bool(ndc)), float(nf), float(ff),
-                                      L.ptr(packed), L.stream()), "cfnerf_rays_setup")
-        if torch.is_tensor(near):
-            packed[:, 6] = near.reshape(-1).to(packed)
-        if torch.is_tensor(far):
-            packed[:, 7] = far.reshape(-1).to(packed)
+        _need_gpu(rays[1], "rays")
+        sh = tuple(rays[1].shape)
+        packed = _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far)
 
     all_ret = render_rays(packed, **kwargs)                                   # one launch (see docstring)
     for k in all_ret:

@@ -14,21 +14,12 @@ using namespace cfnerf;
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* fmt, ...) {
+int cfnerf::fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
-}
-#define HIPCHK(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(CFNERF_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-extern "C" void cfnerf_set_error_(const char* msg) {      // used by the other translation units; hidden (not exported)
-    std::snprintf(g_err, sizeof g_err, "%s", msg);
 }
 
 // device-side part of cfnerf_model_create; on failure the caller destroys the partially built handle
@@ -73,31 +64,62 @@ size_t cfnerf::workspace_bytes_for(const cfnerf_cfg& c, int64_t n, int s, int k)
     return Stash::carve(nullptr, nullptr, c, n, s, k, build_layout(c).total);
 }
 
+static int flow_math_bits(const cfnerf_model* m) {
+    return m->flow_math == 0 ? 0 : (CFNERF_F_FLOW_MATH_SET | (m->flow_math == 2 ? CFNERF_F_FLOW_MATH_FAST : 0));
+}
+
 // Point the stash at its block for an (N,S,K) batch.  A caller-provided block (cfnerf_model_set_workspace) is never
 // grown: too small is an error.  A model-owned block is (re)allocated here - the only place the train path allocates.
-int cfnerf::stash_bind(cfnerf_model* m, int64_t n, int s, int k, char* err, size_t errlen) {
+static int stash_bind(cfnerf_model* m, int64_t n, int s, int k) {
     Stash& q = m->stash;
     if (q.base && q.bound_N == n && q.bound_S == s && q.bound_K == k) return CFNERF_OK;
     const size_t need = Stash::carve(nullptr, nullptr, m->cfg, n, s, k, m->layout.total);
     if (need > q.cap) {
-        if (q.base && !q.owned) {
-            std::snprintf(err, errlen, "the workspace handed to cfnerf_model_set_workspace holds %zu bytes but N=%lld S=%d K=%d needs %zu "
-                          "(size it with cfnerf_workspace_bytes)", q.cap, (long long)n, s, k, need);
-            return CFNERF_E_NOMEM;
-        }
-        if (hipDeviceSynchronize() != hipSuccess) { std::snprintf(err, errlen, "hipDeviceSynchronize failed"); return CFNERF_E_HIP; }
+        if (q.base && !q.owned)
+            return fail(CFNERF_E_NOMEM, "the workspace handed to cfnerf_model_set_workspace holds %zu bytes but N=%lld S=%d K=%d needs %zu "
+                        "(size it with cfnerf_workspace_bytes)", q.cap, (long long)n, s, k, need);
+        if (hipDeviceSynchronize() != hipSuccess) return fail(CFNERF_E_HIP, "hipDeviceSynchronize failed");
         q.release();
         void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) {
-            std::snprintf(err, errlen, "workspace allocation of %zu bytes failed (N=%lld S=%d K=%d)", need, (long long)n, s, k);
-            return CFNERF_E_NOMEM;
-        }
+        if (hipMalloc(&p, need) != hipSuccess)
+            return fail(CFNERF_E_NOMEM, "workspace allocation of %zu bytes failed (N=%lld S=%d K=%d)", need, (long long)n, s, k);
         q.base = static_cast<char*>(p); q.cap = need; q.owned = true;
     }
     q.used = Stash::carve(&q, q.base, m->cfg, n, s, k, m->layout.total);
     q.bound_N = n; q.bound_S = s; q.bound_K = k;
     q.valid = false;
     ++q.bind_serial;
+    return CFNERF_OK;
+}
+
+// The arguments every fused forward launch shares: the weights, the flag word and - for a STASH launch - the model's one stash,
+// bound for (n, s) (a cfnerf_network_fwd launch binds it as ONE "ray" of P samples, `points`) and handed to this forward: its
+// streams, the Q4 layout decision and a new generation (older backward passes are refused).
+static int forward_args(cfnerf_model* m, FwdArgs& a, int flags, int64_t n, int s, int K, bool points) {
+    a.wp = m->d_packed; a.wp16 = m->d_packed16; a.flat = m->flat;
+    a.K = K; a.flags = (flags & 0xffff) | flow_math_bits(m);
+    if (!(flags & CFNERF_F_STASH)) return CFNERF_OK;
+    if (int rc = stash_bind(m, n, s, K)) return rc;
+    Stash& q = m->stash;
+    a.st_enc = q.enc; a.st_gd = q.gd; a.st_h = q.h; a.st_feat = q.feat; a.st_v = q.v; a.st_ha = q.ha; a.st_hr = q.hr;
+    a.st_theta = q.theta;
+    a.st_mbits = reinterpret_cast<uint32_t*>(q.mbits);
+    q.n_tiles = n * (int64_t)((s + kTileM - 1) / kTileM);
+    a.n_tiles = q.n_tiles;
+    a.st_raw = q.raw;                    // the backward reads the model's OWN (tile-transposed) copy: the caller may drop its tensor,
+                                         // and a caller's raw is written by the same launch (rounds 1-4: a device-to-device copy after it)
+    q.N = n; q.S = s; q.K = K; q.flags = flags; q.valid = true; q.points = points;
+    q.q4 = (s % kTileM == 0) && m->precision == 0;      // whole tiles, fp32 mode: the wide streams take the Q4 layout (cfnerf_device.h)
+    a.q4 = q.q4;
+    ++q.generation;
+    return CFNERF_OK;
+}
+
+// the fused forward of a ray launch, between the timing events of cfnerf_timing_enable
+static int timed_fused_fwd(cfnerf_model* m, const FwdArgs& a, bool train, hipStream_t st, int* grid) {
+    if (m->timing) HIPCHK(hipEventRecord(m->fr0[m->fwd_launches % kFwdRing], st));
+    HIPCHK(launch_fused_fwd(a, m->plan.tab, 0, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, grid));
+    if (m->timing) { HIPCHK(hipEventRecord(m->fr1[m->fwd_launches % kFwdRing], st)); ++m->fwd_launches; }
     return CFNERF_OK;
 }
 
@@ -228,10 +250,6 @@ int cfnerf_sample_points(const float* rays, const float* t_vals, const float* t_
     return CFNERF_OK;
 }
 
-static int flow_math_bits(const cfnerf_model* m) {
-    return m->flow_math == 0 ? 0 : (CFNERF_F_FLOW_MATH_SET | (m->flow_math == 2 ? CFNERF_F_FLOW_MATH_FAST : 0));
-}
-
 static int check_common(cfnerf_model* m, int K) {
     if (!m) return fail(CFNERF_E_INVALID, "model is NULL");
     if (!m->flat) return fail(CFNERF_E_INVALID, "cfnerf_model_set_params has not been called");
@@ -256,41 +274,23 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
     const bool train = flags & CFNERF_F_TRAIN;
     if (train && !entropy_out) return fail(CFNERF_E_INVALID, "TRAIN needs entropy_out");
     FwdArgs a{};
-    a.wp = m->d_packed; a.wp16 = m->d_packed16; a.flat = m->flat;
     a.rays = rays; a.t_vals = t_vals; a.t_rand = z_vals_opt ? nullptr : t_rand; a.z_in = z_vals_opt; a.eps = eps;
-    a.N = N; a.S = S; a.K = K; a.P = N * (int64_t)S; a.flags = (flags & 0xffff) | flow_math_bits(m);
+    a.N = N; a.S = S; a.P = N * (int64_t)S;
     a.rgb_map = rgb_map; a.disp = disp_map; a.depth = depth_map;
     a.raw = raw_opt; a.weights = weights_opt; a.pts = pts_opt; a.kstats = kstats_opt;
     a.ent_partials = train ? m->d_ent_partials : nullptr;
     a.enc_scratch = m->d_enc_scratch;
-    if ((flags & CFNERF_F_STASH) && !maps) return fail(CFNERF_E_INVALID, "STASH needs the per-K maps");
-    if (flags & CFNERF_F_STASH) {
-        char why[256];
-        if (int rc = stash_bind(m, N, S, K, why, sizeof why)) return fail(rc, "%s", why);
-        Stash& q = m->stash;
-        a.st_enc = q.enc; a.st_gd = q.gd; a.st_h = q.h; a.st_feat = q.feat; a.st_v = q.v; a.st_ha = q.ha; a.st_hr = q.hr;
-        a.st_theta = q.theta; a.st_z = q.z; a.st_at = q.at;
-        a.st_mbits = reinterpret_cast<uint32_t*>(q.mbits);
-        q.n_tiles = N * (int64_t)((S + kTileM - 1) / kTileM);
-        a.n_tiles = q.n_tiles;
-        a.st_raw = q.raw;                    // the backward reads the model's OWN (tile-transposed) copy: the caller may drop its tensor,
-                                             // and a caller's raw_opt is written by the same launch (rounds 1-4: a device-to-device copy after it)
-        // (q.rays and m->d_eps, the backward's own copies of the step's rays and latents, are written by the copy blocks of the
-        //  entropy_finalize launch below - the forward itself reads the caller's)
-        q.N = N; q.S = S; q.K = K; q.flags = flags; q.valid = true; q.points = false;
-        q.q4 = (S % kTileM == 0) && m->precision == 0;      // whole tiles, fp32 mode: the wide streams take the Q4 layout (cfnerf_device.h)
-        a.q4 = q.q4;
-        ++q.generation;                      // this forward now owns the one stash: older backward passes are refused
-    }
+    const bool keep = flags & CFNERF_F_STASH;
+    if (keep && !maps) return fail(CFNERF_E_INVALID, "STASH needs the per-K maps");
+    if (int rc = forward_args(m, a, flags, N, S, K, false)) return rc;
+    if (keep) { a.st_z = m->stash.z; a.st_at = m->stash.at; }
+    // (with STASH, q.rays and m->d_eps, the backward's own copies of the step's rays and latents, are written by the copy blocks of the
+    //  entropy_finalize launch below - the forward itself reads the caller's)
     int grid = 0;
-    if (m->timing) HIPCHK(hipEventRecord(m->fr0[m->fwd_launches % kFwdRing], st));
-    HIPCHK(launch_fused_fwd(a, m->plan.tab, 0, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, &grid));
-    if (m->timing) { HIPCHK(hipEventRecord(m->fr1[m->fwd_launches % kFwdRing], st)); ++m->fwd_launches; }
-    if (train) {
-        const bool keep = flags & CFNERF_F_STASH;
+    if (int rc = timed_fused_fwd(m, a, train, st, &grid)) return rc;
+    if (train)
         HIPCHK(launch_entropy_finalize(m->d_ent_partials, grid, m->flat, eps, K, (double)a.P * K, entropy_out, keep ? m->d_eps : nullptr, rays,
                                        keep ? m->stash.rays : nullptr, N * 11, st));
-    }
     return CFNERF_OK;
 }
 
@@ -304,16 +304,12 @@ int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, 
     if ((gt_opt == nullptr) != (sqerr_opt == nullptr)) return fail(CFNERF_E_INVALID, "gt_opt and sqerr_opt must be given together");
     if (flags & (CFNERF_F_TRAIN | CFNERF_F_STASH)) return fail(CFNERF_E_INVALID, "cfnerf_render_eval is the eval branch only");
     FwdArgs a{};
-    a.wp = m->d_packed; a.wp16 = m->d_packed16; a.flat = m->flat;
     a.rays = rays; a.t_vals = t_vals; a.eps = eps;
-    a.N = N; a.S = S; a.K = K; a.P = N * (int64_t)S; a.flags = (flags & 0xffff) | flow_math_bits(m);
+    a.N = N; a.S = S; a.P = N * (int64_t)S;
     a.kstats = kstats; a.gt = gt_opt; a.sqerr = sqerr_opt; a.enc_scratch = m->d_enc_scratch;
+    if (int rc = forward_args(m, a, flags, N, S, K, false)) return rc;
     int grid = 0;
-    hipStream_t st = (hipStream_t)s;
-    if (m->timing) HIPCHK(hipEventRecord(m->fr0[m->fwd_launches % kFwdRing], st));
-    HIPCHK(launch_fused_fwd(a, m->plan.tab, 0, false, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, &grid));
-    if (m->timing) { HIPCHK(hipEventRecord(m->fr1[m->fwd_launches % kFwdRing], st)); ++m->fwd_launches; }
-    return CFNERF_OK;
+    return timed_fused_fwd(m, a, false, (hipStream_t)s, &grid);
 }
 
 int cfnerf_sample_pdf(const float* rays, const float* t_vals, const float* t_rand, int flags, const float* weights, const float* u,
@@ -337,25 +333,11 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
     if (train && !entropy_out) return fail(CFNERF_E_INVALID, "TRAIN needs entropy_out");
     hipStream_t st = (hipStream_t)s;
     FwdArgs a{};
-    a.wp = m->d_packed; a.wp16 = m->d_packed16; a.flat = m->flat;
-    a.eps = eps; a.x = x; a.P = P; a.N = 0; a.S = 1; a.K = K; a.flags = (flags & 0xffff) | flow_math_bits(m); a.raw = raw;
+    a.eps = eps; a.x = x; a.P = P; a.N = 0; a.S = 1; a.raw = raw;
     a.ent_partials = train ? m->d_ent_partials : nullptr;
-    if (flags & CFNERF_F_STASH) {            // points-mode stash: the workspace is bound as ONE "ray" of P samples
-        char why[256];
-        if (int rc = stash_bind(m, 1, (int)P, K, why, sizeof why)) return fail(rc, "%s", why);
-        Stash& q = m->stash;
-        a.st_enc = q.enc; a.st_gd = q.gd; a.st_h = q.h; a.st_feat = q.feat; a.st_v = q.v; a.st_ha = q.ha; a.st_hr = q.hr;
-        a.st_theta = q.theta;
-        a.st_mbits = reinterpret_cast<uint32_t*>(q.mbits);
-        q.n_tiles = (P + kTileM - 1) / kTileM;
-        a.n_tiles = q.n_tiles;
-        a.st_raw = q.raw;                    // the backward reads the model's OWN (tile-transposed) copy; the caller's raw is written by the same launch
-        if (!train) HIPCHK(hipMemcpyAsync(m->d_eps, eps, (size_t)K * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));   // (else: entropy_finalize keeps them)
-        q.N = 1; q.S = (int)P; q.K = K; q.flags = flags; q.valid = true; q.points = true;
-        q.q4 = (P % kTileM == 0) && m->precision == 0;
-        a.q4 = q.q4;
-        ++q.generation;
-    }
+    if (int rc = forward_args(m, a, flags, 1, (int)P, K, true)) return rc;      // points-mode stash: ONE "ray" of P samples
+    if ((flags & CFNERF_F_STASH) && !train)      // (else: entropy_finalize keeps them)
+        HIPCHK(hipMemcpyAsync(m->d_eps, eps, (size_t)K * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
     int grid = 0;
     HIPCHK(launch_fused_fwd(a, m->plan.tab, 1, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, &grid));
     if (train)

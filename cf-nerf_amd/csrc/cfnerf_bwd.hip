@@ -19,7 +19,6 @@
 #include "cfnerf_bwd.h"
 #include "cfnerf_dwplan.h"
 
-#include <cstdarg>
 #include <cstdio>
 
 namespace cfnerf {
@@ -1203,24 +1202,6 @@ hipError_t bwd_set_attributes(int W, int ha) {
 
 using namespace cfnerf;
 
-static thread_local char g_berr[512] = "";
-extern "C" const char* cfnerf_last_error(void);
-// error text is shared with the ABI file through this hook
-extern "C" void cfnerf_set_error_(const char* msg);
-static int bfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_berr, sizeof g_berr, fmt, ap);
-    va_end(ap);
-    cfnerf_set_error_(g_berr);
-    return code;
-}
-#define BHIP(expr)                                                                               \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return bfail(CFNERF_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 // build (once per model) the weight-gradient tile list, the bias map and their device copies
 int cfnerf::ensure_bwd_plan(cfnerf_model* m) {
     BwdPlan& B = m->bwd;
@@ -1289,21 +1270,21 @@ extern "C" {
 
 int cfnerf_loss_fwd_bwd(const float* rgb_map, const float* target, const float* entropy, int64_t N, int K, float beta1,
                         int64_t n_total, float* d_rgb_map, float* scalars_out, cfnerf_stream s) {
-    if (N < 0 || K < 1 || n_total < N) return bfail(CFNERF_E_INVALID, "bad N/K/n_total");
+    if (N < 0 || K < 1 || n_total < N) return fail(CFNERF_E_INVALID, "bad N/K/n_total");
     if (N == 0) return CFNERF_OK;
-    if (!rgb_map || !target || !d_rgb_map || !scalars_out) return bfail(CFNERF_E_INVALID, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(scalars_out) % 8) return bfail(CFNERF_E_INVALID, "scalars_out must be 8-byte aligned");
+    if (!rgb_map || !target || !d_rgb_map || !scalars_out) return fail(CFNERF_E_INVALID, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(scalars_out) % 8) return fail(CFNERF_E_INVALID, "scalars_out must be 8-byte aligned");
     hipStream_t st = (hipStream_t)s;
-    BHIP(hipMemsetAsync(scalars_out, 0, 4 * sizeof(float), st));        // the two 64-bit fixed-point accumulators live in these 16 bytes
+    HIPCHK(hipMemsetAsync(scalars_out, 0, 4 * sizeof(float), st));        // the two 64-bit fixed-point accumulators live in these 16 bytes
     if (K >= kLossWideK)
         hipLaunchKernelGGL(loss_kernel<8>, dim3((unsigned)((N * 3 * 8 + kLossThreads - 1) / kLossThreads)), dim3(kLossThreads), 0, st, rgb_map, target,
                            N, K, n_total, d_rgb_map, reinterpret_cast<long long*>(scalars_out));
     else
         hipLaunchKernelGGL(loss_kernel<1>, dim3((unsigned)((N * 3 + kLossThreads - 1) / kLossThreads)), dim3(kLossThreads), 0, st, rgb_map, target,
                            N, K, n_total, d_rgb_map, reinterpret_cast<long long*>(scalars_out));
-    BHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1), 0, st, entropy, beta1, n_total, scalars_out);
-    BHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return CFNERF_OK;
 }
 
@@ -1312,15 +1293,15 @@ int cfnerf_loss_fwd_bwd(const float* rgb_map, const float* target, const float* 
 static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generation, const float* d_out, const float* d_depth_map,
                             const float* d_entropy, float* grad_flat, int accumulate, cfnerf_stream s) {
     Stash& q = m->stash;
-    if (!q.valid) return bfail(CFNERF_E_INVALID, "no stashed forward: call cfnerf_render_fwd / cfnerf_network_fwd with CFNERF_F_STASH first");
+    if (!q.valid) return fail(CFNERF_E_INVALID, "no stashed forward: call cfnerf_render_fwd / cfnerf_network_fwd with CFNERF_F_STASH first");
     if (stash_generation != q.generation)
-        return bfail(CFNERF_E_INVALID, "stale stash: this backward belongs to STASH forward #%llu but the model's one stash now holds "
+        return fail(CFNERF_E_INVALID, "stale stash: this backward belongs to STASH forward #%llu but the model's one stash now holds "
                      "forward #%llu (a later grad-enabled forward overwrote it; run each backward before the next STASH forward)",
                      (unsigned long long)stash_generation, (unsigned long long)q.generation);
     if (q.points != points)
-        return bfail(CFNERF_E_INVALID, points ? "the stashed forward is a cfnerf_render_fwd (ray) launch: differentiate it with cfnerf_render_bwd"
+        return fail(CFNERF_E_INVALID, points ? "the stashed forward is a cfnerf_render_fwd (ray) launch: differentiate it with cfnerf_render_bwd"
                                               : "the stashed forward is a cfnerf_network_fwd (points) launch: differentiate it with cfnerf_network_bwd");
-    if (!points && q.S > 4096) return bfail(CFNERF_E_UNSUPPORTED, "backward supports S <= 4096");
+    if (!points && q.S > 4096) return fail(CFNERF_E_UNSUPPORTED, "backward supports S <= 4096");
     hipStream_t st = (hipStream_t)s;
     if (int rc = ensure_bwd_plan(m)) return rc;
     BwdPlan& B = m->bwd;
@@ -1335,21 +1316,21 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
     if (B.bind_serial != q.bind_serial || B.q4 != q.q4) {      // (the tile descriptors carry operand pointers AND operand layouts)
         B.cur ^= 1;
         DwHost& Hs = B.host[B.cur];
-        if (Hs.uploaded) BHIP(hipEventSynchronize(Hs.uploaded));     // the upload made from THIS set two rebuilds ago is long done
-        else BHIP(hipEventCreateWithFlags(&Hs.uploaded, hipEventDisableTiming));
+        if (Hs.uploaded) HIPCHK(hipEventSynchronize(Hs.uploaded));     // the upload made from THIS set two rebuilds ago is long done
+        else HIPCHK(hipEventCreateWithFlags(&Hs.uploaded, hipEventDisableTiming));
         int ns_max = 1;
-        if (const char* why = build_dw_plan(c, L, q, P, m->n_cu, Hs, &B.n_blocks_wide, &ns_max)) return bfail(CFNERF_E_UNSUPPORTED, "%s", why);
+        if (const char* why = build_dw_plan(c, L, q, P, m->n_cu, Hs, &B.n_blocks_wide, &ns_max)) return fail(CFNERF_E_UNSUPPORTED, "%s", why);
         finish_segs(L, B, Hs);
-        if (Hs.segs.size() > 256) return bfail(CFNERF_E_UNSUPPORTED, "too many parameter tensors");
-        BHIP(hipMemsetAsync(q.partials, 0, (size_t)ns_max * n_params * sizeof(float), st));
+        if (Hs.segs.size() > 256) return fail(CFNERF_E_UNSUPPORTED, "too many parameter tensors");
+        HIPCHK(hipMemsetAsync(q.partials, 0, (size_t)ns_max * n_params * sizeof(float), st));
         auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
-        BHIP(up(q.tiles, Hs.tiles.data(), Hs.tiles.size() * sizeof(DwTile)));
-        BHIP(up(q.tiles_small, Hs.tiles_small.data(), Hs.tiles_small.size() * sizeof(DwTile)));
-        BHIP(up(q.blocks, Hs.blocks.data(), Hs.blocks.size() * sizeof(DwBlock)));
-        BHIP(up(q.blocks_small, Hs.blocks_small.data(), Hs.blocks_small.size() * sizeof(DwBlock)));
-        BHIP(up(q.segs, Hs.segs.data(), Hs.segs.size() * sizeof(RedSeg)));
-        BHIP(up(q.bias_maps, B.bias_maps.data(), B.bias_maps.size() * sizeof(BiasMap)));
-        BHIP(hipEventRecord(Hs.uploaded, st));
+        HIPCHK(up(q.tiles, Hs.tiles.data(), Hs.tiles.size() * sizeof(DwTile)));
+        HIPCHK(up(q.tiles_small, Hs.tiles_small.data(), Hs.tiles_small.size() * sizeof(DwTile)));
+        HIPCHK(up(q.blocks, Hs.blocks.data(), Hs.blocks.size() * sizeof(DwBlock)));
+        HIPCHK(up(q.blocks_small, Hs.blocks_small.data(), Hs.blocks_small.size() * sizeof(DwBlock)));
+        HIPCHK(up(q.segs, Hs.segs.data(), Hs.segs.size() * sizeof(RedSeg)));
+        HIPCHK(up(q.bias_maps, B.bias_maps.data(), B.bias_maps.size() * sizeof(BiasMap)));
+        HIPCHK(hipEventRecord(Hs.uploaded, st));
         B.bind_serial = q.bind_serial;
         B.q4 = q.q4;
     }
@@ -1358,7 +1339,7 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
     // ---- 1. first stage -> g_theta (+ base-Gaussian partials)
     int ksplit = 1;
     int64_t gms_rows = 0;
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev0[1], st));
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev0[1], st));
     if (!points) {
         TailArgs ta{};
         ta.raw = q.raw; ta.theta = q.theta; ta.at = q.at; ta.z = q.z; ta.rays = q.rays; ta.eps = m->d_eps; ta.flat = m->flat;
@@ -1367,15 +1348,15 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
         ksplit = tail_parts(N, q.K, std::min(m->n_cu, kMaxCu));      // 1, 2 or 4: the parts of a ray are waves of ONE 4-wave workgroup and
         ta.ksplit = ksplit;                                          // meet in LDS, so ONE g_theta row per point leaves the kernel
         gms_rows = N * ksplit;
-        BHIP(launch_tail_bwd(ta, N, ksplit, st));
+        HIPCHK(launch_tail_bwd(ta, N, ksplit, st));
     } else {
         unsigned grid = 0;
-        BHIP(launch_flows_bwd(q.raw, q.theta, m->d_eps, m->flat, d_out, d_entropy, P, q.K, q.g_theta, q.gms, &grid, st));
+        HIPCHK(launch_flows_bwd(q.raw, q.theta, m->d_eps, m->flat, d_out, d_entropy, P, q.K, q.g_theta, q.gms, &grid, st));
         gms_rows = (int64_t)grid * kWaves;                       // one row per wave (waves past P contribute zeros)
     }
     hipLaunchKernelGGL(reduce_gms_kernel, dim3(1), dim3(256), 0, st, q.gms, gms_rows, m->flat, d_entropy, grad_flat, accumulate);
-    BHIP(hipGetLastError());
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev1[1], st));
+    HIPCHK(hipGetLastError());
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev1[1], st));
 
     // ---- 2. fused backward-data (+ bias partials and their reduction: every bias gradient is final here)
     BwdArgs ba{};                                              // (q.dbp needs no memset: every launched workgroup starts its row on its first tile)
@@ -1385,15 +1366,15 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
     ba.mbits = reinterpret_cast<const uint32_t*>(q.mbits); ba.n_tiles = q.n_tiles; ba.S = q.S; ba.dbp = q.dbp;      // (points: ONE "ray" of S = P samples)
     ba.db_h = B.db_h; ba.db_feat = B.db_feat; ba.db_v = B.db_v; ba.db_ha = B.db_ha; ba.db_hr = B.db_hr; ba.db_theta = B.db_theta;
     int grid_bd = 0;
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev0[2], st));
-    BHIP(launch_bwd_data(ba, m->plan.tab, m->precision, st, &grid_bd));
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev1[2], st));
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev0[2], st));
+    HIPCHK(launch_bwd_data(ba, m->plan.tab, m->precision, st, &grid_bd));
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev1[2], st));
     hipLaunchKernelGGL(reduce_bias_kernel, dim3((unsigned)((B.nb + 63) / 64)), dim3(1024), 0, st, q.dbp, grid_bd, B.nb,
                        q.bias_maps, (int)B.bias_maps.size(), grad_flat, accumulate);
-    BHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
 
     // ---- 3. weight gradients + reductions
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev0[3], st));
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev0[3], st));
     if (!Hc.blocks.empty()) {
         if (m->precision == PREC_BF16X3)
             hipLaunchKernelGGL(dw_big_kernel<PREC_BF16X3>, dim3((unsigned)Hc.blocks.size()), dim3(kDwThreads), kDwBigLds, st,
@@ -1401,101 +1382,101 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
         else
             hipLaunchKernelGGL(dw_big_kernel<PREC_F32>, dim3((unsigned)Hc.blocks.size()), dim3(kDwThreads), kDwBigLds, st,
                                q.tiles, q.blocks, q.partials, n_params);
-        BHIP(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     // tensors fed by big tiles only (+ the zeros of dead tensors): final now.  ev_early lets a multi-GPU caller start
     // exchanging B.early_off / early_cnt while the small jobs below still compute - IF it ever asked for those ranges
     // (cfnerf_grad_early_ranges: the two-bucket exchange).  Otherwise nothing can be waiting between the two reductions and they
     // are ONE launch after the small jobs (the same sums in the same order; one launch of ~14 us less per step).
     const unsigned red_grid = (unsigned)((n_params + 255) / 256);
-    if (!B.ev_early) BHIP(hipEventCreateWithFlags(&B.ev_early, hipEventDisableTiming));
+    if (!B.ev_early) HIPCHK(hipEventCreateWithFlags(&B.ev_early, hipEventDisableTiming));
     if (B.early_wanted) {
         hipLaunchKernelGGL(reduce_weights_kernel, dim3(red_grid), dim3(256), 0, st, q.partials, q.segs, (int)Hc.segs.size(), n_params, grad_flat, 1, accumulate);
-        BHIP(hipGetLastError());
-        BHIP(hipEventRecord(B.ev_early, st));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(B.ev_early, st));
     }
     if (!Hc.blocks_small.empty()) {
         hipLaunchKernelGGL(dw_small_kernel, dim3((unsigned)Hc.blocks_small.size()), dim3(kDsThreads), kDwSmallLds, st,
                            q.tiles_small, q.blocks_small, q.partials, n_params);
-        BHIP(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(reduce_weights_kernel, dim3(red_grid), dim3(256), 0, st, q.partials, q.segs, (int)Hc.segs.size(), n_params, grad_flat,
                        B.early_wanted ? 0 : 2, accumulate);
-    BHIP(hipGetLastError());
-    if (!B.early_wanted) BHIP(hipEventRecord(B.ev_early, st));      // (a waiter on the event still sees final gradients: everything is final here)
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev1[3], st));
+    HIPCHK(hipGetLastError());
+    if (!B.early_wanted) HIPCHK(hipEventRecord(B.ev_early, st));      // (a waiter on the event still sees final gradients: everything is final here)
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev1[3], st));
     return CFNERF_OK;
 }
 
 int cfnerf_render_bwd(cfnerf_model* m, uint64_t stash_generation, const float* d_rgb_map, const float* d_depth_map,
                       const float* d_entropy, float* grad_flat, cfnerf_stream s) {
-    if (!m || !d_rgb_map || !grad_flat) return bfail(CFNERF_E_INVALID, "NULL argument");
+    if (!m || !d_rgb_map || !grad_flat) return fail(CFNERF_E_INVALID, "NULL argument");
     return backward_stashed(m, false, stash_generation, d_rgb_map, d_depth_map, d_entropy, grad_flat, 0, s);
 }
 
 int cfnerf_render_bwd_accumulate(cfnerf_model* m, uint64_t stash_generation, const float* d_rgb_map, const float* d_depth_map,
                                  const float* d_entropy, float* grad_flat, cfnerf_stream s) {
-    if (!m || !d_rgb_map || !grad_flat) return bfail(CFNERF_E_INVALID, "NULL argument");
+    if (!m || !d_rgb_map || !grad_flat) return fail(CFNERF_E_INVALID, "NULL argument");
     return backward_stashed(m, false, stash_generation, d_rgb_map, d_depth_map, d_entropy, grad_flat, 1, s);
 }
 
 int cfnerf_network_bwd(cfnerf_model* m, uint64_t stash_generation, const float* d_raw, const float* d_entropy, float* grad_flat,
                        cfnerf_stream s) {
-    if (!m || !grad_flat) return bfail(CFNERF_E_INVALID, "NULL argument");
-    if (!d_raw && !d_entropy) return bfail(CFNERF_E_INVALID, "d_raw and d_entropy are both NULL: nothing to differentiate");
+    if (!m || !grad_flat) return fail(CFNERF_E_INVALID, "NULL argument");
+    if (!d_raw && !d_entropy) return fail(CFNERF_E_INVALID, "d_raw and d_entropy are both NULL: nothing to differentiate");
     return backward_stashed(m, true, stash_generation, d_raw, nullptr, d_entropy, grad_flat, 0, s);
 }
 
 int cfnerf_composite_bwd(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K, int white_bkgd,
                          const float* d_rgb_map, const float* d_disp_map, const float* d_depth_map, const float* d_weights, float* d_raw,
                          cfnerf_stream s) {
-    if (N < 0 || S < 1 || K < 1) return bfail(CFNERF_E_INVALID, "bad N/S/K");
-    if (S > 64 * kCompMaxChunks) return bfail(CFNERF_E_UNSUPPORTED, "cfnerf_composite_bwd supports S <= %d", 64 * kCompMaxChunks);
+    if (N < 0 || S < 1 || K < 1) return fail(CFNERF_E_INVALID, "bad N/S/K");
+    if (S > 64 * kCompMaxChunks) return fail(CFNERF_E_UNSUPPORTED, "cfnerf_composite_bwd supports S <= %d", 64 * kCompMaxChunks);
     if (N == 0) return CFNERF_OK;
-    if (!raw || !z_vals || !rays_d || !d_rgb_map || !d_raw) return bfail(CFNERF_E_INVALID, "NULL argument");
-    if ((int64_t)S * K * 16 >= (1ll << 31)) return bfail(CFNERF_E_UNSUPPORTED, "cfnerf_composite_bwd: S * K * 16 bytes per ray must stay below 2 GiB");
+    if (!raw || !z_vals || !rays_d || !d_rgb_map || !d_raw) return fail(CFNERF_E_INVALID, "NULL argument");
+    if ((int64_t)S * K * 16 >= (1ll << 31)) return fail(CFNERF_E_UNSUPPORTED, "cfnerf_composite_bwd: S * K * 16 bytes per ray must stay below 2 GiB");
 #define CFN_COMPB(KG, FAST) hipLaunchKernelGGL((composite_bwd_kernel<KG, FAST>), dim3((unsigned)((N + kWaves - 1) / kWaves)), dim3(kThreads), 0, \
                        (hipStream_t)s, raw, z_vals, rays_d, N, S, K, white_bkgd, d_rgb_map, d_disp_map, d_depth_map, d_weights, d_raw)
     if (K <= 4) CFN_COMPB(4, false);                // (the same split as launch_composite: forward and adjoint share their arithmetic)
     else if (K < kFastFlowsK) CFN_COMPB(8, false);
     else CFN_COMPB(8, true);
 #undef CFN_COMPB
-    BHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return CFNERF_OK;
 }
 
 // The flat ranges of grad_flat that are final when the early event of the LAST cfnerf_render_bwd fires (they do not
 // depend on the batch: only on which tensors are fed by big tiles).  Returns the number of ranges (<= max), < 0 on error.
 int cfnerf_grad_early_ranges(cfnerf_model* m, int64_t* offsets, int64_t* counts, int max_ranges) {
-    if (!m || !offsets || !counts) return bfail(CFNERF_E_INVALID, "NULL argument");
-    if (m->bwd.early_off.empty()) return bfail(CFNERF_E_INVALID, "no backward has run on this model yet");
+    if (!m || !offsets || !counts) return fail(CFNERF_E_INVALID, "NULL argument");
+    if (m->bwd.early_off.empty()) return fail(CFNERF_E_INVALID, "no backward has run on this model yet");
     const int n = (int)m->bwd.early_off.size();
-    if (n > max_ranges) return bfail(CFNERF_E_INVALID, "%d ranges, room for %d", n, max_ranges);
+    if (n > max_ranges) return fail(CFNERF_E_INVALID, "%d ranges, room for %d", n, max_ranges);
     for (int i = 0; i < n; ++i) { offsets[i] = m->bwd.early_off[i]; counts[i] = m->bwd.early_cnt[i]; }
     m->bwd.early_wanted = true;            // from the next backward on the early tensors are reduced (and ev_early recorded) BEFORE the small-job launch
     return n;
 }
 
 int cfnerf_stream_wait_grad_early(cfnerf_model* m, cfnerf_stream waiter) {
-    if (!m) return bfail(CFNERF_E_INVALID, "model is NULL");
-    if (!m->bwd.ev_early) return bfail(CFNERF_E_INVALID, "no backward has run on this model yet");
-    BHIP(hipStreamWaitEvent((hipStream_t)waiter, m->bwd.ev_early, 0));
+    if (!m) return fail(CFNERF_E_INVALID, "model is NULL");
+    if (!m->bwd.ev_early) return fail(CFNERF_E_INVALID, "no backward has run on this model yet");
+    HIPCHK(hipStreamWaitEvent((hipStream_t)waiter, m->bwd.ev_early, 0));
     return CFNERF_OK;
 }
 
 int cfnerf_adam_step(cfnerf_model* m, float* flat_params, const float* grad_flat, float* exp_avg, float* exp_avg_sq,
                      int64_t step, float lr, float grad_scale, cfnerf_stream s) {
-    if (!m || !flat_params || !grad_flat || !exp_avg || !exp_avg_sq) return bfail(CFNERF_E_INVALID, "NULL argument");
-    if (step < 1) return bfail(CFNERF_E_INVALID, "step is 1-based");
+    if (!m || !flat_params || !grad_flat || !exp_avg || !exp_avg_sq) return fail(CFNERF_E_INVALID, "NULL argument");
+    if (step < 1) return fail(CFNERF_E_INVALID, "step is 1-based");
     hipStream_t st = (hipStream_t)s;
     const int64_t n = m->layout.total;
     const double bc1 = 1.0 - std::pow(0.9, (double)step), bc2 = 1.0 - std::pow(0.999, (double)step);
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev0[4], st));
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev0[4], st));
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, flat_params, grad_flat, exp_avg, exp_avg_sq, n,
                        (float)(lr / bc1), (float)(1.0 / std::sqrt(bc2)), grad_scale);
-    BHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     int rc = cfnerf_model_set_params(m, flat_params, s);
-    if (m->timing == 1) BHIP(hipEventRecord(m->ev1[4], st));
+    if (m->timing == 1) HIPCHK(hipEventRecord(m->ev1[4], st));
     return rc;
 }
 

@@ -154,8 +154,13 @@ struct cfnerf_model {
 };
 
 namespace cfnerf {
-// (re)bind the stash pointers for an (N,S,K) batch; grows a model-owned block, rejects a caller block that is too small
-int stash_bind(cfnerf_model* m, int64_t n, int s, int k, char* err, size_t errlen);
+// the library's one error facility: sets the thread-local text cfnerf_last_error() returns (cfnerf_abi.hip) and returns `code`
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+#define HIPCHK(expr)                                                                            \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess) return cfnerf::fail(CFNERF_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
 int ensure_bwd_plan(cfnerf_model* m);
 size_t workspace_bytes_for(const cfnerf_cfg& c, int64_t n, int s, int k);
 hipError_t bwd_set_attributes(int W, int ha);             // dynamic-LDS limits of the backward kernels, per device

@@ -16,8 +16,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib as L
-from .api import _pose_arg
+from .api import _pack_rays
 
 
 class RayPool:
@@ -37,15 +36,11 @@ class RayPool:
         poses = torch.as_tensor(poses, dtype=torch.float32).cpu()        # the poses travel in kernel arguments: one fetch for all views
         if not images.is_cuda:
             images = images.cuda()
-        dev = images.device
-        lib = L.lib()
         n = self.H * self.W
         chunks = []
-        packed = torch.empty(n, 11, device=dev)
+        packed = torch.empty(n, 11, device=images.device)
         for v in i_train:
-            arr, _keep = _pose_arg(poses[int(v)])
-            L.check(lib.cfnerf_rays_setup(self.H, self.W, self.focal, arr, None, None, n, 0, 0, 0.0, 1.0, L.ptr(packed), L.stream()),
-                    "cfnerf_rays_setup")
+            _pack_rays(self.H, self.W, self.focal, c2w=poses[int(v)], out=packed)
             rays = torch.stack([packed[:, 0:3], packed[:, 3:6], images[int(v)].reshape(n, 3)], 1)      # [n, ro+rd+rgb, 3]
             chunks.append(rays)
         self.rays_rgb = torch.cat(chunks, 0)                                                           # [(V_train)*H*W, 3, 3]

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .api import _pose_arg, _unwrap, render, t_vals_table
+from .api import _pack_rays, _render_fwd, _unwrap, render, t_vals_table
 
 
 def render_path_train(render_poses, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0):
@@ -87,36 +87,29 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
     if t_vals is None:
         t_vals = t_vals_table(dev)
     S = t_vals.shape[0]
-    lib = L.lib()
-    packed = torch.empty(n, 11, device=dev)
-    arr, _keep = _pose_arg(c2w)
-    L.check(lib.cfnerf_rays_setup(int(H), int(W), float(focal), arr, None, None, n, r0 * W, int(bool(ndc)), float(near), float(far),
-                                  L.ptr(packed), L.stream()), "cfnerf_rays_setup")
+    packed = _pack_rays(H, W, focal, c2w=c2w, n=n, pixel0=r0 * W, ndc=ndc, near=near, far=far, device=dev)
     net._sync()
     eps = net.eval_eps()
     flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
-    kst = torch.empty(n, 8, device=dev)
-    rgb = disp = depth = None
-    if want_maps:
-        rgb, disp, depth = torch.empty(n, 3, K, device=dev), torch.empty(n, K, device=dev), torch.empty(n, K, device=dev)
     sq = None
     if want_maps:
-        L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(packed), L.ptr(t_vals), None, None, L.ptr(eps), n, S, K, flags, L.ptr(rgb), L.ptr(disp),
-                                      L.ptr(depth), None, None, None, L.ptr(kst), None, L.stream()), "cfnerf_render_fwd")
+        o = _render_fwd(net, packed, t_vals, None, eps, flags, kstats=True, entropy=False)
+        kst = o['kstats']
         if gt is not None:
             sq = (kst[:, 0:3] - gt.to(dev, torch.float32).reshape(n, 3)) ** 2
     else:
+        kst = torch.empty(n, 8, device=dev)
         g = None
         if gt is not None:
             g = gt.to(dev, torch.float32).reshape(n, 3).contiguous()
             sq = torch.empty(n, 3, device=dev)
-        L.check(lib.cfnerf_render_eval(net.handle, L.ptr(packed), L.ptr(t_vals), L.ptr(eps), n, S, K, flags, L.ptr(g), L.ptr(kst), L.ptr(sq),
-                                       L.stream()), "cfnerf_render_eval")
+        L.check(L.lib().cfnerf_render_eval(net.handle, L.ptr(packed), L.ptr(t_vals), L.ptr(eps), n, S, K, flags, L.ptr(g), L.ptr(kst), L.ptr(sq),
+                                           L.stream()), "cfnerf_render_eval")
     h = r1 - r0
     out = dict(rgb_mean=kst[:, 0:3].reshape(h, W, 3), rgb_unc=kst[:, 3:6].reshape(h, W, 3), disp_mean=kst[:, 6].reshape(h, W),
                depth_mean=kst[:, 7].reshape(h, W))
     if want_maps:
-        out.update(rgb_map=rgb.reshape(h, W, 3, K), disp_map=disp.reshape(h, W, K), depth_map=depth.reshape(h, W, K))
+        out.update(rgb_map=o['rgb_map'].reshape(h, W, 3, K), disp_map=o['disp_map'].reshape(h, W, K), depth_map=o['depth_map'].reshape(h, W, K))
     if sq is not None:
         out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
     return out

@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .api import NeRF_Flows, _f32c, _unwrap
+from .api import NeRF_Flows, _f32c, _pack_rays, _unwrap, t_vals_table
 
 
 def backward_available() -> bool:
@@ -212,24 +212,37 @@ class Trainer:
             self.d_rgb = torch.empty(N, 3, K, device=dev)
             self._buf_n = (N, K)
 
+    def _pass(self, a, b, t_vals, t_rand, eps, S, flags, target, beta, scalars, entropy, d_ent, grad=None, accumulate=False, z_vals=None,
+              weights=None):
+        """One pass over rows [a, b) of the packed rays into the persistent buffers: the fused forward (``t_rand`` / ``z_vals`` and the
+        optional ``weights [N,S,K]`` output are per-ray too and sliced alike) and, given a ``grad`` buffer, a STASH forward followed by the
+        KDE-NLL loss (+ ``beta`` * entropy; means over the step's whole shard) into ``scalars`` and the backward into ``grad``
+        (``accumulate``: added to what it holds)."""
+        net, lib, st = self.net, L.lib(), L.stream()
+        rows = lambda t: t[a:b] if t is not None else None
+        n, K = b - a, net.K_samples
+        L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed[a:b]), L.ptr(t_vals), L.ptr(rows(t_rand)), L.ptr(rows(z_vals)), L.ptr(eps),
+                                      n, S, K, flags | (L.F_STASH if grad is not None else 0), L.ptr(self.rgb_map[a:b]), L.ptr(self.disp[a:b]),
+                                      L.ptr(self.depth[a:b]), None, L.ptr(rows(weights)), None, None, L.ptr(entropy), st), "cfnerf_render_fwd")
+        if grad is None:
+            return
+        L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map[a:b]), L.ptr(target[a:b]), L.ptr(entropy), n, K, C.c_float(beta),
+                                        self.packed.shape[0] * self.world, L.ptr(self.d_rgb[a:b]), L.ptr(scalars), st), "cfnerf_loss_fwd_bwd")
+        gen = lib.cfnerf_model_stash_generation(net.handle)
+        bwd = lib.cfnerf_render_bwd_accumulate if accumulate else lib.cfnerf_render_bwd
+        L.check(bwd(net.handle, gen, L.ptr(self.d_rgb[a:b]), None, L.ptr(d_ent) if self.beta1 else None, L.ptr(grad), st),
+                "cfnerf_render_bwd_accumulate" if accumulate else "cfnerf_render_bwd")
+
     def forward_backward(self, H, W, focal, rays, target, t_rand=None, eps=None, near=0., far=1., ndc=True,
                          lindisp=False, white_bkgd=False, perturb=1., t_vals=None, **_ignored):
         """Forward + loss + backward of this rank's shard.  Leaves the (un-reduced) gradient in ``self.grad``."""
-        net, lib = self.net, L.lib()
+        net = self.net
         dev = net.flat.device
-        rays_o, rays_d = rays
-        ro, rd = _f32c(rays_o.reshape(-1, 3)), _f32c(rays_d.reshape(-1, 3))
-        N, K = rd.shape[0], net.K_samples
-        if t_vals is None:
-            if not hasattr(self, "_tv"):
-                from .api import t_vals_table
-                self._tv = t_vals_table(dev)
-            t_vals = self._tv
+        N, K = rays[1].reshape(-1, 3).shape[0], net.K_samples
+        t_vals = t_vals_table(dev) if t_vals is None else t_vals            # (cached per device)
         S = t_vals.shape[0]
         self._buffers(N, K)
-        st = L.stream()
-        L.check(lib.cfnerf_rays_setup(H, W, float(focal), None, L.ptr(ro), L.ptr(rd), N, 0, int(bool(ndc)), float(near), float(far),
-                                      L.ptr(self.packed), st), "cfnerf_rays_setup")
+        _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far, out=self.packed)
         if perturb > 0. and t_rand is None:
             t_rand = torch.rand(N, S, device=dev)
         if perturb <= 0.:
@@ -238,49 +251,34 @@ class Trainer:
             eps = net.draw_eps()
         eps = _f32c(eps)
         net._sync()
-        flags = L.F_STASH | L.F_TRAIN | (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
+        flags = L.F_TRAIN | (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
         n_sl = self.n_slices(N)
         t_rand = _f32c(t_rand) if t_rand is not None else None
         target = _f32c(target)
-        if n_sl == 1:
-            net.ensure_workspace(N, S, K)
-            L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed), L.ptr(t_vals), L.ptr(t_rand),
-                                          None, L.ptr(eps), N, S, K, flags, L.ptr(self.rgb_map), L.ptr(self.disp), L.ptr(self.depth),
-                                          None, None, None, None, L.ptr(self.entropy), st), "cfnerf_render_fwd")
-            L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map), L.ptr(target), L.ptr(self.entropy), N, K,
-                                            C.c_float(self.beta1 / self.world), N * self.world, L.ptr(self.d_rgb), L.ptr(self.scalars), st),
-                    "cfnerf_loss_fwd_bwd")
-            gen = lib.cfnerf_model_stash_generation(net.handle)
-            L.check(lib.cfnerf_render_bwd(net.handle, gen, L.ptr(self.d_rgb), None, L.ptr(self.d_ent) if self.beta1 else None,
-                                          L.ptr(self.grad), st), "cfnerf_render_bwd")
-            return self.grad
-        # ---- the shard in n_sl equal slices: every loss term is taken with n_total = the FULL batch and beta1 / (world n_sl) on the slice's
-        # entropy (equal slices: the mean of the slice means is the batch mean), so the slice gradients and the scalar contributions ADD
+        # the shard in n_sl equal slices: every loss term is taken with n_total = the FULL batch and beta1 / (world n_sl) on the slice's
+        # entropy (equal slices: the mean of the slice means is the batch mean), so the slice gradients and the scalar contributions ADD.
+        # One slice writes its scalars and entropy straight into the step's own buffers.
         Ns = N // n_sl
         net.ensure_workspace(Ns, S, K)
-        if getattr(self, "_sl_n", None) != n_sl:
-            dev = net.flat.device
-            self._d_ent_sl = torch.tensor([self.beta1 / (self.world * n_sl)], device=dev)
-            self._sc_sl, self._ent_sl = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
-            self._sl_n = n_sl
-        beta_sl = C.c_float(self.beta1 / (self.world * n_sl))
-        sc_sum, ent_sum = torch.zeros(4, device=net.flat.device), torch.zeros(1, device=net.flat.device)
+        if n_sl == 1:
+            sc, ent, d_ent = self.scalars, self.entropy, self.d_ent
+        else:
+            if getattr(self, "_sl_n", None) != n_sl:
+                self._d_ent_sl = torch.tensor([self.beta1 / (self.world * n_sl)], device=dev)
+                self._sc_sl, self._ent_sl = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
+                self._sl_n = n_sl
+            sc, ent, d_ent = self._sc_sl, self._ent_sl, self._d_ent_sl
+            sc_sum, ent_sum = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         for i in range(n_sl):
-            a, b = i * Ns, (i + 1) * Ns
-            L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed[a:b]), L.ptr(t_vals), L.ptr(t_rand[a:b]) if t_rand is not None else None,
-                                          None, L.ptr(eps), Ns, S, K, flags, L.ptr(self.rgb_map[a:b]), L.ptr(self.disp[a:b]), L.ptr(self.depth[a:b]),
-                                          None, None, None, None, L.ptr(self._ent_sl), st), "cfnerf_render_fwd")
-            L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map[a:b]), L.ptr(target[a:b]), L.ptr(self._ent_sl), Ns, K, beta_sl, N * self.world,
-                                            L.ptr(self.d_rgb[a:b]), L.ptr(self._sc_sl), st), "cfnerf_loss_fwd_bwd")
-            gen = lib.cfnerf_model_stash_generation(net.handle)
-            bwd = lib.cfnerf_render_bwd if i == 0 else lib.cfnerf_render_bwd_accumulate
-            L.check(bwd(net.handle, gen, L.ptr(self.d_rgb[a:b]), None, L.ptr(self._d_ent_sl) if self.beta1 else None, L.ptr(self.grad), st),
-                    "cfnerf_render_bwd" if i == 0 else "cfnerf_render_bwd_accumulate")
-            sc_sum += self._sc_sl
-            ent_sum += self._ent_sl
-        self.scalars[:3] = sc_sum[:3]
-        self.scalars[3] = -10.0 * torch.log10(sc_sum[2])                # HLP:16 on the batch's mse
-        self.entropy.copy_(ent_sum / n_sl)
+            self._pass(i * Ns, (i + 1) * Ns, t_vals, t_rand, eps, S, flags, target, self.beta1 / (self.world * n_sl), sc, ent, d_ent,
+                       grad=self.grad, accumulate=i > 0)
+            if n_sl > 1:
+                sc_sum += sc
+                ent_sum += ent
+        if n_sl > 1:
+            self.scalars[:3] = sc_sum[:3]
+            self.scalars[3] = -10.0 * torch.log10(sc_sum[2])                # HLP:16 on the batch's mse
+            self.entropy.copy_(ent_sum / n_sl)
         return self.grad
 
     def n_slices(self, N):
@@ -292,16 +290,15 @@ class Trainer:
             n += 1
         return n
 
-    def step(self, H, W, focal, rays, target, **kw):
-        """One full train step.  Returns the device tensor [loss, loss_nll, mse, psnr] of the local shard."""
-        kw = {k: v for k, v in kw.items() if k in ("t_rand", "eps", "near", "far", "ndc", "lindisp", "white_bkgd", "perturb", "t_vals")}
+    def _step(self, forward_backward, exchange, H, W, focal, rays, target, kw):
+        """Body of step / step_hierarchical: the step's latents, forward + backward, the gradient exchange, Adam, re-pack."""
         dist_on = self.world > 1 or self.force_allreduce
         if kw.get("eps") is None and dist_on:
             kw["eps"] = self._step_eps()
-        self.forward_backward(H, W, focal, rays, target, **kw)
+        forward_backward(H, W, focal, rays, target, **kw)
         if dist_on:
             self._queue_next_eps()
-            self._timed_exchange(self._exchange)
+            self._timed_exchange(exchange)
             self._take_next_eps()
         lr = lr_at(self.lrate, self.lrate_decay, self.start, self.t)
         self.t += 1
@@ -312,6 +309,11 @@ class Trainer:
         net.mark_packed()
         net.params_serial += 1
         return self.scalars
+
+    def step(self, H, W, focal, rays, target, **kw):
+        """One full train step.  Returns the device tensor [loss, loss_nll, mse, psnr] of the local shard."""
+        kw = {k: v for k, v in kw.items() if k in ("t_rand", "eps", "near", "far", "ndc", "lindisp", "white_bkgd", "perturb", "t_vals")}
+        return self._step(self.forward_backward, self._exchange, H, W, focal, rays, target, kw)
 
     # ---- EXTENSION (not in the reference, SURVEY R1 / 8f-4): coarse + fine sampling through the single network -----
     def forward_backward_hierarchical(self, H, W, focal, rays, target, N_samples=64, N_importance=128, coarse_loss=True, t_rand=None,
@@ -322,15 +324,11 @@ class Trainer:
         ``coarse_loss`` the coarse pass keeps a stash and its own loss term is differentiated too
         (nerf-pytorch adds img2mse(rgb0); here the same KDE-NLL as the fine term), so ``self.grad`` is the gradient of
         loss_fine + loss_coarse.  Returns it; ``self.scalars`` holds the fine pass's [loss, nll, mse, psnr]."""
-        net, lib = self.net, L.lib()
+        net = self.net
         dev = net.flat.device
-        rays_o, rays_d = rays
-        ro, rd = _f32c(rays_o.reshape(-1, 3)), _f32c(rays_d.reshape(-1, 3))
-        N, K, S, Ni = rd.shape[0], net.K_samples, int(N_samples), int(N_importance)
+        N, K, S, Ni = rays[1].reshape(-1, 3).shape[0], net.K_samples, int(N_samples), int(N_importance)
         self._buffers(N, K)
-        st = L.stream()
-        L.check(lib.cfnerf_rays_setup(H, W, float(focal), None, L.ptr(ro), L.ptr(rd), N, 0, int(bool(ndc)), float(near), float(far),
-                                      L.ptr(self.packed), st), "cfnerf_rays_setup")
+        _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far, out=self.packed)
         tv = torch.linspace(0., 1., steps=S).to(dev)
         if perturb > 0.:
             t_rand = _f32c(torch.rand(N, S, device=dev) if t_rand is None else t_rand)
@@ -341,35 +339,22 @@ class Trainer:
         eps = _f32c(net.draw_eps() if eps is None else eps)
         net._sync()
         net.ensure_workspace(N, S + Ni, K)
-        base = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | L.F_TRAIN
+        flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | L.F_TRAIN
         target = _f32c(target)
-        beta_w, n_tot = C.c_float(self.beta1 / self.world), N * self.world
-        d_ent = L.ptr(self.d_ent) if self.beta1 else None
+        loss = (target, self.beta1 / self.world, self.scalars, self.entropy, self.d_ent)
         # 1. coarse pass -> per-sample weights -> resampled depths.  With a coarse loss term the same launch also stashes its
-        #    activations, so the coarse term costs one backward, not a second forward.
+        #    activations and its loss and backward follow at once (before the fine pass replaces the stash), so the coarse term
+        #    costs one backward, not a second forward.
         w0 = torch.empty(N, S, K, device=dev)
-        L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed), L.ptr(tv), L.ptr(t_rand), None, L.ptr(eps), N, S, K,
-                                      base | (L.F_STASH if coarse_loss else 0), L.ptr(self.rgb_map), L.ptr(self.disp), L.ptr(self.depth),
-                                      None, L.ptr(w0), None, None, L.ptr(self.entropy), st), "cfnerf_render_fwd")
-        z_all = torch.empty(N, S + Ni, device=dev)
-        L.check(lib.cfnerf_sample_pdf(L.ptr(self.packed), L.ptr(tv), L.ptr(t_rand), base, L.ptr(w0), L.ptr(u), N, S, K, Ni, L.ptr(z_all), st),
-                "cfnerf_sample_pdf")
-        grad_c = None
-        if coarse_loss:     # 2. coarse loss term and its backward (before the fine pass replaces the stash)
-            L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map), L.ptr(target), L.ptr(self.entropy), N, K, beta_w, n_tot, L.ptr(self.d_rgb),
-                                            L.ptr(self.scalars), st), "cfnerf_loss_fwd_bwd")
-            grad_c = torch.empty_like(self.grad)
-            L.check(lib.cfnerf_render_bwd(net.handle, lib.cfnerf_model_stash_generation(net.handle), L.ptr(self.d_rgb), None, d_ent,
-                                          L.ptr(grad_c), st), "cfnerf_render_bwd")
+        grad_c = torch.empty_like(self.grad) if coarse_loss else None
+        self._pass(0, N, tv, t_rand, eps, S, flags, *loss, grad=grad_c, weights=w0)
+        if coarse_loss:
             self.scalars_coarse = self.scalars.clone()
-        # 3. fine pass on the merged depths, loss, backward
-        L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed), L.ptr(tv), None, L.ptr(z_all), L.ptr(eps), N, S + Ni, K, base | L.F_STASH,
-                                      L.ptr(self.rgb_map), L.ptr(self.disp), L.ptr(self.depth), None, None, None, None,
-                                      L.ptr(self.entropy), st), "cfnerf_render_fwd")
-        L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map), L.ptr(target), L.ptr(self.entropy), N, K, beta_w, n_tot, L.ptr(self.d_rgb),
-                                        L.ptr(self.scalars), st), "cfnerf_loss_fwd_bwd")
-        L.check(lib.cfnerf_render_bwd(net.handle, lib.cfnerf_model_stash_generation(net.handle), L.ptr(self.d_rgb), None, d_ent,
-                                      L.ptr(self.grad), st), "cfnerf_render_bwd")
+        z_all = torch.empty(N, S + Ni, device=dev)
+        L.check(L.lib().cfnerf_sample_pdf(L.ptr(self.packed), L.ptr(tv), L.ptr(t_rand), flags, L.ptr(w0), L.ptr(u), N, S, K, Ni, L.ptr(z_all),
+                                          L.stream()), "cfnerf_sample_pdf")
+        # 2. fine pass on the merged depths, loss, backward
+        self._pass(0, N, tv, None, eps, S + Ni, flags, *loss, grad=self.grad, z_vals=z_all)
         if grad_c is not None:
             self.grad.add_(grad_c)
         self.z_vals = z_all
@@ -377,23 +362,10 @@ class Trainer:
 
     def step_hierarchical(self, H, W, focal, rays, target, **kw):
         """One full train step of the coarse + fine EXTENSION (see forward_backward_hierarchical)."""
-        dist_on = self.world > 1 or self.force_allreduce
-        if kw.get("eps") is None and dist_on:
-            kw["eps"] = self._step_eps()
-        self.forward_backward_hierarchical(H, W, focal, rays, target, **kw)
-        if dist_on:
-            self._queue_next_eps()
-            self._timed_exchange(lambda: allreduce_sum_(self.gbuf, self.world, self.group, self.force_allreduce))
-            self._take_next_eps()
-        lr = lr_at(self.lrate, self.lrate_decay, self.start, self.t)
-        self.t += 1
-        net = self.net
-        L.check(L.lib().cfnerf_adam_step(net.handle, L.ptr(net.flat.data), L.ptr(self.grad), L.ptr(self.exp_avg),
-                                         L.ptr(self.exp_avg_sq), self.t, C.c_float(lr), C.c_float(1.0), L.stream()),
-                "cfnerf_adam_step")
-        net.mark_packed()
-        net.params_serial += 1
-        return self.scalars
+        # always the plain one-bucket all-reduce: this gradient is grad_fine + grad_c, added by torch after the last backward, while
+        # the early-range event that overlap_comm's first bucket waits for fires inside that backward, before the add
+        return self._step(self.forward_backward_hierarchical, lambda: allreduce_sum_(self.gbuf, self.world, self.group, self.force_allreduce),
+                          H, W, focal, rays, target, kw)
 
     @property
     def global_step(self):
