@@ -16,6 +16,12 @@ raises if the library is missing or the tensors are not on a GPU.
 Extra (new) keyword arguments make the reference's hidden randomness explicit:
 ``t_rand [N,S]``, ``eps_alpha [K,1]``, ``eps_rgb [K,3]``.  When left ``None`` they are drawn with
 torch in the reference's order (RUN:524 -> MOD:234 -> MOD:246).
+
+Reference-exact latents (opt-in, ``create_nerf`` with ``args.latent_draws = "netchunk"``): the reference draws a fresh
+latent pair per ``netchunk`` points (RUN:47-64,82; MOD:234,246), so a train batch larger than one netchunk uses several
+latent sets.  In that mode the train branch draws them in the reference's order (``draw_train_randomness``), lays them
+out as one row per ray (``netchunk_eps_rows``) and launches with ``CFNERF_F_EPS_ROWS``; explicit latents are then
+``eps_alpha [C,K,1]`` / ``eps_rgb [C,K,3]``, one pair per netchunk.
 """
 from __future__ import annotations
 
@@ -254,8 +260,91 @@ def reference_init(shapes, netdepth, K_samples=None):
     return vals, latents
 
 
+# --------------------------------------------------------------------------------------------
+# per-netchunk latents (the reference's batchify_rays -> run_network -> batchify nesting, RUN:47-64,82,88-100)
+LATENT_DRAWS = ("launch", "netchunk")
+
+
+def _ray_cuts(N, chunk):
+    """(first ray, rays) of every batchify_rays cut of an N-ray batch (RUN:88-100); ``chunk=None``: one cut."""
+    step = N if not chunk else int(chunk)
+    return [(r0, min(step, N - r0)) for r0 in range(0, N, max(step, 1))]
+
+
+def netchunk_count(N, S, netchunk, chunk=None):
+    """Latent pairs the reference draws for an N-ray train batch of S samples per ray: every ``chunk``-ray cut restarts
+    batchify's count and makes ``ceil(n_c * S / netchunk)`` network calls."""
+    return sum(-(-(n * S) // int(netchunk)) for _, n in _ray_cuts(N, chunk))
+
+
+def netchunk_eps_rows(eps_chunks, N, S, netchunk, chunk=None):
+    """Expand per-netchunk latents ``eps_chunks [C,K,4]`` (in draw order) to ray rows ``[N,K,4]``: ray i gets the latents of
+    the network call that evaluates its points.  Needs ``netchunk % S == 0`` (else the reference switches latents in the
+    middle of a ray, which one row per ray cannot express)."""
+    netchunk, S = int(netchunk), int(S)
+    if netchunk % S:
+        raise NotImplementedError(f"netchunk ({netchunk}) is not a multiple of the samples per ray ({S}): the reference then changes "
+                                  f"latents in the middle of a ray, which per-ray latent rows cannot express")
+    per = netchunk // S                          # rays of one network call
+    idx, base = [], 0
+    for _, n in _ray_cuts(N, chunk):
+        idx.append(base + torch.arange(n) // per)
+        base += -(-(n * S) // netchunk)
+    if eps_chunks.shape[0] != base:
+        raise ValueError(f"{eps_chunks.shape[0]} latent pairs given; N={N}, S={S}, netchunk={netchunk}, chunk={chunk} needs {base}")
+    idx = torch.cat(idx) if idx else torch.zeros(0, dtype=torch.long)
+    return eps_chunks.index_select(0, idx.to(eps_chunks.device)).contiguous()
+
+
+def netchunk_eps_point_rows(eps_chunks, P, netchunk):
+    """Per-netchunk latents ``[C,K,4]`` as one row per point ``[P,K,4]`` (batchify over P points, RUN:47-64)."""
+    idx = torch.arange(int(P)) // int(netchunk)
+    if eps_chunks.shape[0] != -(-int(P) // int(netchunk)):
+        raise ValueError(f"{eps_chunks.shape[0]} latent pairs given; P={P}, netchunk={netchunk} needs {-(-int(P) // int(netchunk))}")
+    return eps_chunks.index_select(0, idx.to(eps_chunks.device)).contiguous()
+
+
+def _draw_pairs(n, K):
+    """n latent pairs from torch's CPU generator, eps_alpha then eps_rgb per network call (MOD:234,246), as ``[n,K,4]``."""
+    out = torch.empty(n, K, 4)
+    for c in range(n):
+        ea = torch.empty([K, 1]).normal_()
+        er = torch.empty([K, 3]).normal_()
+        out[c, :, :3], out[c, :, 3:] = er, ea
+    return out
+
+
+def draw_train_randomness(N, S, K, chunk, netchunk, perturb, raw_noise_std=0.):
+    """The randomness of one reference train render of N rays, from torch's CPU generator in the reference's order.  Per
+    ``chunk``-ray cut (RUN:88-100): ``t_rand [n_c,S]`` if ``perturb > 0`` (RUN:524), then per network call of the cut
+    eps_alpha, eps_rgb (MOD:234,246), then - if ``raw_noise_std > 0`` - the ``randn([n_c,S,K])`` raw2outputs draws and never
+    uses (RUN:434).  Returns ``(t_rand [N,S] or None, eps_chunks [C,K,4])``."""
+    netchunk = int(netchunk)
+    tr, eps = [], []
+    for _, n in _ray_cuts(N, chunk):
+        if perturb > 0.:
+            tr.append(torch.rand([n, S]))
+        eps.append(_draw_pairs(-(-(n * S) // netchunk), K))
+        if raw_noise_std > 0.:
+            torch.randn([n, S, K])
+    t_rand = (torch.cat(tr, 0) if tr else torch.zeros(0, S)) if perturb > 0. else None
+    return t_rand, (torch.cat(eps, 0) if eps else torch.zeros(0, K, 4))
+
+
+def _per_netchunk_latents(eps_alpha, eps_rgb):
+    """True for explicit per-netchunk latents ``eps_alpha [C,K,1]`` / ``eps_rgb [C,K,3]``, False for one ``[K,1]`` / ``[K,3]`` set or none."""
+    if eps_alpha is None and eps_rgb is None:
+        return False
+    if eps_alpha is None or eps_rgb is None or eps_alpha.dim() != eps_rgb.dim() or eps_alpha.dim() not in (2, 3):
+        raise ValueError("eps_alpha and eps_rgb go together: [K,1] / [K,3] (one set) or [C,K,1] / [C,K,3] (one pair per netchunk)")
+    return eps_alpha.dim() == 3
+
+
 def _latents(model, eps_alpha, eps_rgb, train, device):
     """[K,4] latents of a launch: the explicit ``eps_rgb | eps_alpha`` when given, else fresh train draws or the fixed eval ones."""
+    if _per_netchunk_latents(eps_alpha, eps_rgb):
+        raise ValueError("per-netchunk latents [C,K,1] / [C,K,3] cannot be one launch's [K,4] set (train branch of render_rays / "
+                         "NeRF_Flows.forward only)")
     if eps_alpha is not None or eps_rgb is not None:
         return torch.cat([eps_rgb, eps_alpha], -1).to(device, torch.float32).contiguous()
     return model.draw_eps() if train else model.eval_eps()
@@ -310,6 +399,8 @@ class NeRF_Flows(nn.Module):
         self._h = h
         self._packed_version = None
         self._next_eps = None          # explicit latents handed from render_rays to an unfused network_query_fn
+        self.latent_draws = "launch"   # "netchunk": per-netchunk train latents like the reference (create_nerf: args.latent_draws)
+        self.netchunk = 1024 * 64      # points per network call of the reference (netchunk_per_gpu * n_gpus, RUN:82,384)
         self._ws = None                # train-step workspace: a torch-owned block lent to the library
 
     # ---- parameters ------------------------------------------------------------------------
@@ -460,8 +551,19 @@ class NeRF_Flows(nn.Module):
         P, K = xf.shape[0], self.K_samples
         if self._next_eps is not None and eps_alpha is None and eps_rgb is None:
             eps = self._next_eps                                    # latents chosen by the enclosing render_rays call
+        elif not is_test and (self.latent_draws == "netchunk" or _per_netchunk_latents(eps_alpha, eps_rgb)):
+            # per-netchunk latents (batchify, RUN:47-64): explicit [C,K,1] / [C,K,3] or C fresh pairs, one row per point
+            if eps_alpha is not None or eps_rgb is not None:
+                chunks = torch.cat([eps_rgb, eps_alpha], -1).to(torch.float32)
+            else:
+                chunks = _draw_pairs(-(-P // self.netchunk), K)
+            eps = netchunk_eps_point_rows(chunks, P, self.netchunk).to(self.device)
         else:
             eps = _latents(self, eps_alpha, eps_rgb, not is_test, self.device)
+        if eps.dim() == 3 and eps.shape[0] != P:
+            # (point rows from render_rays cover the whole batch: a network_query_fn of its own must hand all of it to ONE call)
+            raise ValueError(f"latent rows for {eps.shape[0]} points, the call has {P}: in netchunk mode render_rays hands one latent row "
+                             f"per point of the whole batch, so a custom network_query_fn must evaluate all of them in one NeRF_Flows call")
         if torch.is_grad_enabled() and self.flat.requires_grad and not is_test and P > 0:
             # the reference's forward is an autograd graph (MOD:188-291): so is this one - cfnerf_network_fwd with the
             # activation stash, differentiated by cfnerf_network_bwd (gradients reach the parameters; x is a constant)
@@ -504,7 +606,12 @@ def _refuse_changed_params(model, token, pack_serial):
 
 
 def _network_fwd(model, xf, eps, K, flags):
-    """cfnerf_network_fwd of the encoded points ``xf [P,90]`` into new ``raw [P,K,4]`` and a zeroed entropy accumulator ``[1]``."""
+    """cfnerf_network_fwd of the encoded points ``xf [P,90]`` into new ``raw [P,K,4]`` and a zeroed entropy accumulator ``[1]``.
+    ``eps`` is the launch's ``[K,4]`` or one row per point ``[P,K,4]`` (CFNERF_F_EPS_ROWS)."""
+    if eps.dim() == 3:
+        if eps.shape[0] != xf.shape[0]:
+            raise ValueError(f"latent rows for {eps.shape[0]} points, the launch has {xf.shape[0]}")
+        flags |= L.F_EPS_ROWS
     raw = torch.empty(xf.shape[0], K, 4, device=xf.device)
     ent = torch.zeros(1, device=xf.device)
     L.check(L.lib().cfnerf_network_fwd(model.handle, L.ptr(xf), L.ptr(eps), xf.shape[0], K, flags, L.ptr(raw), L.ptr(ent), L.stream()),
@@ -520,8 +627,9 @@ class _NetworkFn(torch.autograd.Function):
 
     @staticmethod
     def _forward_stash(model, xf, eps):
-        model.ensure_workspace(1, xf.shape[0], eps.shape[0])
-        raw, ent = _network_fwd(model, xf, eps, eps.shape[0], L.F_TRAIN | L.F_STASH)
+        K = eps.shape[-2]
+        model.ensure_workspace(1, xf.shape[0], K)
+        raw, ent = _network_fwd(model, xf, eps, K, L.F_TRAIN | L.F_STASH)
         return raw, ent, L.lib().cfnerf_model_stash_generation(model.handle)
 
     @staticmethod
@@ -621,6 +729,8 @@ def batchify(fn, chunk):
         if isinstance(m, NeRF_Flows) and torch.is_grad_enabled() and m.flat.requires_grad and not is_test:
             # one launch = the model's one stash; chunks would each replace it and the backward would re-run their forwards
             return fn(inputs, is_val, is_test)
+        if isinstance(m, NeRF_Flows) and m._next_eps is not None and m._next_eps.dim() == 3:
+            return fn(inputs, is_val, is_test)          # latent rows of the whole batch: its network calls are already in them
         A, B = [], []
         for i in range(0, inputs.shape[0], chunk):
             a, b = fn(inputs[i:i + chunk], is_val, is_test)
@@ -660,7 +770,11 @@ def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True,
     ``disp_map`` / ``depth_map [N,K]`` (``maps``), ``raw [N,S,K,4]``, ``weights [N,S,K]``, ``pts [N,S,3]``, ``kstats [N,8]`` and the
     zeroed accumulator ``entropy [1]``; an output that was not asked for is None.  S is that of ``z_vals [N,S]`` (explicit depths,
     which the library then prefers to ``t_rand``) or of the sample table ``t_vals``."""
-    N, K = rays.shape[0], eps.shape[0]
+    N, K = rays.shape[0], eps.shape[-2]
+    if eps.dim() == 3:                   # one [K,4] row per ray (CFNERF_F_EPS_ROWS): the kernels read row i for ray i, so exactly N rows
+        if eps.shape[0] != N:
+            raise ValueError(f"latent rows for {eps.shape[0]} rays, the launch has {N} (per-netchunk latents go through netchunk_eps_rows)")
+        flags |= L.F_EPS_ROWS
     S = z_vals.shape[1] if z_vals is not None else t_vals.shape[0]
     dev = rays.device
     new = lambda want, *shape: torch.empty(*shape, device=dev) if want else None
@@ -678,10 +792,11 @@ class _RenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, model, rays, t_vals, t_rand, eps, flags, want_pts, z_vals):
-        N, K = rays.shape[0], eps.shape[0]
+        N, K = rays.shape[0], eps.shape[-2]
         model.ensure_workspace(N, z_vals.shape[1] if z_vals is not None else t_vals.shape[0], K)
         o = _render_fwd(model, rays, t_vals, t_rand, eps, flags | L.F_STASH, z_vals, raw=True, pts=want_pts)
         ctx.model = model
+        ctx.eps = eps               # latent rows: the stash reads the caller's buffer until the backward (cfnerf.h, CFNERF_F_EPS_ROWS)
         ctx.n_params = flat.numel()
         ctx.generation = L.lib().cfnerf_model_stash_generation(model.handle)
         ctx.params_at, ctx.pack_serial = _params_token(model), model.pack_serial
@@ -708,16 +823,21 @@ class _RenderFn(torch.autograd.Function):
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, uniformsample, retraw=False,
                 lindisp=False, K_samples=0, perturb=0., N_importance=0, network_fine=None, white_bkgd=False,
                 raw_noise_std=0., verbose=False, pytest=False, t_rand=None, eps_alpha=None, eps_rgb=None,
-                t_vals=None, retweights=False, hierarchical_extension=False, u_fine=None):
+                t_vals=None, retweights=False, hierarchical_extension=False, u_fine=None, chunk=None):
     """Volumetric rendering of a ray batch (RUN:457-553) in ONE fused launch.
 
     Returns ``{'rgb_map' [N,3,K], 'disp_map' [N,K], 'depth_map' [N,K]}`` plus ``raw``, ``loss_entropy``
     and ``pts`` when ``is_train`` (RUN:542-547).  ``retraw``, ``uniformsample``, ``K_samples``, ``verbose``
     are accepted and never read, like the reference; ``N_importance > 0`` / ``network_fine`` - which the
     reference silently ignores (there is no fine pass) - are rejected.
+
+    A model in ``latent_draws = "netchunk"`` mode takes its train latents per netchunk (module docstring): ``chunk`` is then the
+    ray cut of the reference's batchify_rays that the draw layout follows (``render`` passes its own; None = one cut).
     """
     _need_gpu(ray_batch, "ray_batch")
     if hierarchical_extension and N_importance and N_importance > 0:
+        if is_train and _unwrap(network_fn).latent_draws == "netchunk":
+            raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
         return _render_rays_hierarchical(ray_batch, network_fn, N_samples, N_importance, is_train, lindisp, perturb, white_bkgd,
                                          t_rand, eps_alpha, eps_rgb, t_vals, u_fine)
     if N_importance and N_importance > 0 or network_fine is not None:
@@ -736,6 +856,22 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
         t_vals = t_vals.to(dev, torch.float32).contiguous()
     N, S, K = ray_batch.shape[0], t_vals.shape[0], model.K_samples
     rays = _f32c(ray_batch)
+    eps_rows = None
+    per_chunk = _per_netchunk_latents(eps_alpha, eps_rgb)
+    if per_chunk and not is_train:
+        raise ValueError("per-netchunk latents eps_alpha [C,K,1] / eps_rgb [C,K,3] are train-branch only (the eval branch uses the fixed latents)")
+    if is_train and (model.latent_draws == "netchunk" or per_chunk):
+        # per-netchunk latents as ray rows (explicit [C,K,1] / [C,K,3] mean the same in either mode); implicit draws (netchunk mode) in the
+        # reference's order, cut by cut (draw_train_randomness)
+        if eps_alpha is None and eps_rgb is None:
+            tr, chunks = draw_train_randomness(N, S, K, chunk, model.netchunk, perturb, raw_noise_std)
+            t_rand = tr if t_rand is None else t_rand
+        elif per_chunk:
+            chunks = torch.cat([eps_rgb, eps_alpha], -1).to(torch.float32)
+        else:
+            chunks = None                                   # an explicit [K,1] / [K,3]: one set for the launch, as in "launch" mode
+        if chunks is not None:
+            eps_rows = netchunk_eps_rows(chunks, N, S, model.netchunk, chunk).to(dev)
     # randomness, in the reference's order: t_rand (RUN:524), eps_alpha (MOD:234), eps_rgb (MOD:246)
     if perturb > 0.:
         if t_rand is None:
@@ -743,12 +879,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
         t_rand = _f32c(t_rand.to(dev))
     else:
         t_rand = None
-    eps = _latents(model, eps_alpha, eps_rgb, is_train, dev)
+    eps = _latents(model, eps_alpha, eps_rgb, is_train, dev) if eps_rows is None else eps_rows
     flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_TRAIN if is_train else 0)
     model._sync()
 
     fused = network_query_fn is None or getattr(network_query_fn, "_cfnerf_fused", False)
     if not fused:
+        if eps_rows is not None:                            # the network sees points: one row per point (ray row repeated S times)
+            eps = eps_rows.repeat_interleave(S, 0)
         return _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_rand, eps, is_train, lindisp, white_bkgd)
 
     if is_train and N > 0 and torch.is_grad_enabled() and model.flat.requires_grad:
@@ -862,6 +1000,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         sh = tuple(rays[1].shape)
         packed = _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far)
 
+    kwargs.setdefault("chunk", chunk)                 # (read only by per-netchunk latents: their layout follows the ray cuts, RUN:88-100)
     all_ret = render_rays(packed, **kwargs)                                   # one launch (see docstring)
     for k in all_ret:
         if k != 'loss_entropy' and k != 'loss_entropy_uniformsample':         # RUN:163
@@ -880,7 +1019,7 @@ def default_args(**over):
         h_alpha_size=32, h_rgb_size=64, z_size=4, n_flows=4, type_flows="triangular", n_hidden=128, netchunk_per_gpu=1024 * 64,
         n_gpus=1, lrate=5e-4, lrate_decay=250, ft_path=None, basedir="./logs/", dataname="leaves", expname="cfnerf", no_reload=True,
         index_step=-1, is_train=True, uniformsample=False, perturb=1.0, N_samples=128, white_bkgd=False, raw_noise_std=0.0,
-        dataset_type="llff", no_ndc=False, lindisp=False, beta1=0.0, device=torch.device("cuda"))
+        dataset_type="llff", no_ndc=False, lindisp=False, beta1=0.0, device=torch.device("cuda"), latent_draws="launch")
     for k, v in over.items():
         setattr(a, k, v)
     return a
@@ -945,6 +1084,11 @@ def create_nerf(args):
     if not hasattr(args, "device") or args.device is None:
         args.device = torch.device("cuda")
     model = _DataParallelShim(NeRF_Flows(args))
+    latent_draws = getattr(args, "latent_draws", "launch")       # not a reference flag: "netchunk" = the reference's per-netchunk latents
+    if latent_draws not in LATENT_DRAWS:
+        raise ValueError(f"latent_draws must be one of {LATENT_DRAWS}, got {latent_draws!r}")
+    model.module.latent_draws = latent_draws
+    model.module.netchunk = args.netchunk_per_gpu * max(1, getattr(args, "n_gpus", 1))
     grad_vars = list(model.parameters())
 
     def network_query_fn(inputs, viewdirs, network_fn, is_val, is_test):

@@ -109,6 +109,7 @@ static int forward_args(cfnerf_model* m, FwdArgs& a, int flags, int64_t n, int s
     a.st_raw = q.raw;                    // the backward reads the model's OWN (tile-transposed) copy: the caller may drop its tensor,
                                          // and a caller's raw is written by the same launch (rounds 1-4: a device-to-device copy after it)
     q.N = n; q.S = s; q.K = K; q.flags = flags; q.valid = true; q.points = points;
+    q.eps_rows = (flags & CFNERF_F_EPS_ROWS) ? a.eps : nullptr;
     q.q4 = (s % kTileM == 0) && m->precision == 0;      // whole tiles, fp32 mode: the wide streams take the Q4 layout (cfnerf_device.h)
     a.q4 = q.q4;
     ++q.generation;
@@ -282,6 +283,8 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
     a.enc_scratch = m->d_enc_scratch;
     const bool keep = flags & CFNERF_F_STASH;
     if (keep && !maps) return fail(CFNERF_E_INVALID, "STASH needs the per-K maps");
+    const bool rows = flags & CFNERF_F_EPS_ROWS;
+    if (rows && !train) return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_ROWS is a train-branch mode (the eval branch uses the fixed [K,4] latents)");
     if (int rc = forward_args(m, a, flags, N, S, K, false)) return rc;
     if (keep) { a.st_z = m->stash.z; a.st_at = m->stash.at; }
     // (with STASH, q.rays and m->d_eps, the backward's own copies of the step's rays and latents, are written by the copy blocks of the
@@ -289,8 +292,8 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
     int grid = 0;
     if (int rc = timed_fused_fwd(m, a, train, st, &grid)) return rc;
     if (train)
-        HIPCHK(launch_entropy_finalize(m->d_ent_partials, grid, m->flat, eps, K, (double)a.P * K, entropy_out, keep ? m->d_eps : nullptr, rays,
-                                       keep ? m->stash.rays : nullptr, N * 11, st));
+        HIPCHK(launch_entropy_finalize(m->d_ent_partials, grid, m->flat, eps, K, (double)a.P * K, entropy_out, (keep && !rows) ? m->d_eps : nullptr,
+                                       rays, keep ? m->stash.rays : nullptr, N * 11, rows ? N : 0, S, st));
     return CFNERF_OK;
 }
 
@@ -303,6 +306,8 @@ int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, 
     if (K < 2) return fail(CFNERF_E_INVALID, "kstats needs K >= 2 (std * n/(n-1))");
     if ((gt_opt == nullptr) != (sqerr_opt == nullptr)) return fail(CFNERF_E_INVALID, "gt_opt and sqerr_opt must be given together");
     if (flags & (CFNERF_F_TRAIN | CFNERF_F_STASH)) return fail(CFNERF_E_INVALID, "cfnerf_render_eval is the eval branch only");
+    if (flags & CFNERF_F_EPS_ROWS)
+        return fail(CFNERF_E_INVALID, "cfnerf_render_eval uses the fixed [K,4] eval latents: CFNERF_F_EPS_ROWS (per-ray latent rows) is a train-branch mode");
     FwdArgs a{};
     a.rays = rays; a.t_vals = t_vals; a.eps = eps;
     a.N = N; a.S = S; a.P = N * (int64_t)S;
@@ -331,6 +336,8 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
     if (flags & CFNERF_F_STASH) flags |= CFNERF_F_TRAIN;
     const bool train = flags & CFNERF_F_TRAIN;
     if (train && !entropy_out) return fail(CFNERF_E_INVALID, "TRAIN needs entropy_out");
+    const bool rows = flags & CFNERF_F_EPS_ROWS;
+    if (rows && !train) return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_ROWS is a train-branch mode (the eval branch uses the fixed [K,4] latents)");
     hipStream_t st = (hipStream_t)s;
     FwdArgs a{};
     a.eps = eps; a.x = x; a.P = P; a.N = 0; a.S = 1; a.raw = raw;
@@ -342,7 +349,7 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
     HIPCHK(launch_fused_fwd(a, m->plan.tab, 1, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, &grid));
     if (train)
         HIPCHK(launch_entropy_finalize(m->d_ent_partials, grid, m->flat, eps, K, (double)P * K, entropy_out,
-                                       (flags & CFNERF_F_STASH) ? m->d_eps : nullptr, nullptr, nullptr, 0, st));
+                                       ((flags & CFNERF_F_STASH) && !rows) ? m->d_eps : nullptr, nullptr, nullptr, 0, rows ? P : 0, 1, st));
     return CFNERF_OK;
 }
 

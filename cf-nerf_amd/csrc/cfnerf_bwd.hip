@@ -1340,9 +1340,10 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
     int ksplit = 1;
     int64_t gms_rows = 0;
     if (m->timing == 1) HIPCHK(hipEventRecord(m->ev0[1], st));
+    const float* const eps = q.eps_rows ? q.eps_rows : m->d_eps;      // (rows: the caller's buffer; q.flags carries CFNERF_F_EPS_ROWS)
     if (!points) {
         TailArgs ta{};
-        ta.raw = q.raw; ta.theta = q.theta; ta.at = q.at; ta.z = q.z; ta.rays = q.rays; ta.eps = m->d_eps; ta.flat = m->flat;
+        ta.raw = q.raw; ta.theta = q.theta; ta.at = q.at; ta.z = q.z; ta.rays = q.rays; ta.eps = eps; ta.flat = m->flat;
         ta.d_rgb = d_out; ta.d_depth = d_depth_map; ta.d_ent = d_entropy; ta.N = N; ta.P = P; ta.S = q.S; ta.K = q.K; ta.flags = q.flags;
         ta.g_theta = q.g_theta; ta.gms_partials = q.gms;
         ksplit = tail_parts(N, q.K, std::min(m->n_cu, kMaxCu));      // 1, 2 or 4: the parts of a ray are waves of ONE 4-wave workgroup and
@@ -1351,7 +1352,7 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
         HIPCHK(launch_tail_bwd(ta, N, ksplit, st));
     } else {
         unsigned grid = 0;
-        HIPCHK(launch_flows_bwd(q.raw, q.theta, m->d_eps, m->flat, d_out, d_entropy, P, q.K, q.g_theta, q.gms, &grid, st));
+        HIPCHK(launch_flows_bwd(q.raw, q.theta, eps, q.eps_rows ? 1 : 0, m->flat, d_out, d_entropy, P, q.K, q.g_theta, q.gms, &grid, st));
         gms_rows = (int64_t)grid * kWaves;                       // one row per wave (waves past P contribute zeros)
     }
     hipLaunchKernelGGL(reduce_gms_kernel, dim3(1), dim3(256), 0, st, q.gms, gms_rows, m->flat, d_entropy, grad_flat, accumulate);

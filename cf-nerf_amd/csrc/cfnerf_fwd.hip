@@ -91,10 +91,13 @@ static_assert(offsetof(FwdKargs, T) == (sizeof(FwdArgs) + alignof(NetTab) - 1) /
 // Q4 (train, fp32, whole tiles only - launch_fused_fwd picks the variant from FwdArgs::q4): the trunk activations h[0 .. D-1], 8 of the 9.5
 // W-wide units the forward stashes per point, leave as Q4 pieces straight from the accumulator registers (cfnerf_device.h) instead of by
 // rows out of LDS.
-template <int W, int MODE /*0 rays, 1 points*/, bool TRAIN, int PREC, bool Q4 = false>
+// ROWS (train only, CFNERF_F_EPS_ROWS): the latents are one [K,4] row per ray (MODE 0) / per point (MODE 1) instead of one set per
+// launch.  A variant of its own, so the register allocation of the one-set kernels is exactly what it was without the mode.
+template <int W, int MODE /*0 rays, 1 points*/, bool TRAIN, int PREC, bool Q4 = false, bool ROWS = false>
 __global__ __launch_bounds__(FwdCfg<W>::NTHR, 2)
 void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
     static_assert(!Q4 || (TRAIN && PREC == PREC_F32), "the Q4 stash layout exists for the fp32 train variants only");
+    static_assert(!ROWS || TRAIN, "latent rows are a train-branch mode");
     // The arguments live in the kernarg segment, so every per-layer descriptor read is a scalar load from constant
     // memory.  (Through a global pointer the compiler must assume the kernel's own stores may alias the table and issues
     // VECTOR loads with a full wait in front of each layer's first operand fetch: two or three dependent L2 round trips.)
@@ -487,6 +490,11 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
                 fetched_together(f_eps, f_raw, f_weights, f_sraw, f_at, f_flags);
                 const int row = lane_id_opaque();
                 const bool valid = row < rows_valid;
+                // ROWS, ray mode: the latents of this tile's ray - one row for the whole tile (a tile never straddles rays), addressed from
+                // scalar values so the [K,4] reads stay on the scalar path.  Points mode: a row per lane (eps_of below)
+                const float* e_ray = f_eps;
+                if constexpr (ROWS && MODE == 0)
+                    e_ray = f_eps + (int64_t)__builtin_amdgcn_readfirstlane((int)unit) * (K * 4);
                 float th[84];
                 auto load_th = [&]() {          // (the one-latent-at-a-time path keeps the point's flow parameters in registers over its loop)
                     const f32x4* tp = reinterpret_cast<const f32x4*>(act + row * LD);
@@ -507,8 +515,16 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
                 auto flow_phase = [&](auto fast_tag) {
                     constexpr bool FAST = decltype(fast_tag)::value;
                     using M = Num<FAST>;
+                    auto eps_of = [&](const int k) -> f32x4 {
+                        if constexpr (ROWS && MODE == 1) {      // (lanes past the last point read the last point's row: in range, never used)
+                            const int64_t pr = min(p0 + row, A.P - 1);
+                            return *reinterpret_cast<const f32x4*>(f_eps + (pr * K + k) * 4);
+                        } else {
+                            return *reinterpret_cast<const f32x4*>(e_ray + k * 4);
+                        }
+                    };
                     auto one = [&](const int k) {
-                        const f32x4 e = *reinterpret_cast<const f32x4*>(f_eps + k * 4);
+                        const f32x4 e = eps_of(k);
                         float z[3] = {e[0] * r_std[0] + r_mean[0], e[1] * r_std[1] + r_mean[1], e[2] * r_std[2] + r_mean[2]};  // MOD:206/251
                         float a = e[3] * a_std + a_mean;                                               // MOD:200/239
                         float ldr, lda;
@@ -553,7 +569,7 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
                     // for component the operations of one(): the same values, summed into the entropy terms in the same order.
                     auto two = [&](const int k0, const int k1) {
                         using M2 = Num2;
-                        const f32x4 e0 = *reinterpret_cast<const f32x4*>(f_eps + k0 * 4), e1 = *reinterpret_cast<const f32x4*>(f_eps + k1 * 4);
+                        const f32x4 e0 = eps_of(k0), e1 = eps_of(k1);
                         f32x2 z[3], a;
 #pragma unroll
                         for (int c = 0; c < 3; ++c) { f32x2 ec; ec[0] = e0[c]; ec[1] = e1[c]; z[c] = ec * r_std[c] + r_mean[c]; }
@@ -708,13 +724,31 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
 #undef CFN_KARGS
 }
 
+// base-Gaussian log-densities of one [K,4] set of latents, summed over k (MOD:268,283: Normal(mean, std).log_prob of z0 = eps std + mean)
+__device__ __forceinline__ void base_logprob_sums(const float* eps, int K, const float* flat, float& base_a, float& base_r) {
+    const float a_mean = flat[0], a_std = flat[1];
+    base_a = 0.f; base_r = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float a0 = eps[k * 4 + 3] * a_std + a_mean;
+        base_a += -0.5f * (logf(a_std) * 2.f + (a0 - a_mean) * (a0 - a_mean) * (1.f / (a_std * a_std)));
+        for (int c = 0; c < 3; ++c) {
+            const float m = flat[2 + c], sd = flat[5 + c];
+            const float r0 = eps[k * 4 + c] * sd + m;
+            base_r += -0.5f * (logf(sd) * 2.f + (r0 - m) * (r0 - m) * (1.f / (sd * sd)));
+        }
+    }
+}
+
 // loss_entropy = mean(base_a) - mean(ld_a) + mean(base_rgb) - mean(ld_rgb)      (MOD:268,283,286)
 // Blocks past the first are a copy engine: the backward reads the model's OWN copies of the step's rays and latents (the caller may
 // drop its tensors), and as blocks of this launch the two copies cost no launches of their own (they were two hipMemcpyAsync, ~4 us
 // of stream time each, in front of every forward).
+// Latent rows (n_eps_rows > 0, CFNERF_F_EPS_ROWS): the base terms are the point-weighted mean over the rows, each row's sum over k
+// taken exactly as for one [K,4] set and the rows added in double - rows that all equal one set give that set's value bit for bit
+// (every partial sum is an exact integer multiple of it).
 __global__ void entropy_finalize_kernel(const float* partials, int n_part, const float* flat, const float* eps,
                                         int K, double count /* P*K */, float* out, float* eps_keep, const float* rays, float* rays_keep,
-                                        int64_t n_rays_floats) {
+                                        int64_t n_rays_floats, int64_t n_eps_rows, int row_points) {
     if (blockIdx.x > 0) {
         const int64_t i = ((int64_t)blockIdx.x - 1) * blockDim.x + threadIdx.x;
         if (i < n_rays_floats) rays_keep[i] = rays[i];
@@ -722,28 +756,32 @@ __global__ void entropy_finalize_kernel(const float* partials, int n_part, const
     }
     if (eps_keep != nullptr)
         for (int i = threadIdx.x; i < K * 4; i += blockDim.x) eps_keep[i] = eps[i];
-    __shared__ double sh[2][256];
-    double s0 = 0, s1 = 0;
+    __shared__ double sh[4][256];
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
     for (int i = threadIdx.x; i < n_part; i += blockDim.x) { s0 += partials[2 * i]; s1 += partials[2 * i + 1]; }
-    sh[0][threadIdx.x] = s0; sh[1][threadIdx.x] = s1;
+    for (int64_t r = threadIdx.x; r < n_eps_rows; r += blockDim.x) {
+        float ba, br;
+        base_logprob_sums(eps + r * K * 4, K, flat, ba, br);
+        s2 += (double)ba * row_points; s3 += (double)br * row_points;
+    }
+    sh[0][threadIdx.x] = s0; sh[1][threadIdx.x] = s1; sh[2][threadIdx.x] = s2; sh[3][threadIdx.x] = s3;
     __syncthreads();
     for (int d = 128; d >= 1; d >>= 1) {
-        if ((int)threadIdx.x < d) { sh[0][threadIdx.x] += sh[0][threadIdx.x + d]; sh[1][threadIdx.x] += sh[1][threadIdx.x + d]; }
+        if ((int)threadIdx.x < d)
+            for (int j = 0; j < 4; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + d];
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const float a_mean = flat[0], a_std = flat[1];
-        float base_a = 0.f, base_r = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const float a0 = eps[k * 4 + 3] * a_std + a_mean;
-            base_a += -0.5f * (logf(a_std) * 2.f + (a0 - a_mean) * (a0 - a_mean) * (1.f / (a_std * a_std)));
-            for (int c = 0; c < 3; ++c) {
-                const float m = flat[2 + c], sd = flat[5 + c];
-                const float r0 = eps[k * 4 + c] * sd + m;
-                base_r += -0.5f * (logf(sd) * 2.f + (r0 - m) * (r0 - m) * (1.f / (sd * sd)));
-            }
+        double base_a, base_r;
+        if (n_eps_rows > 0) {
+            const double pts = (double)n_eps_rows * row_points;
+            base_a = sh[2][0] / pts; base_r = sh[3][0] / pts;
+        } else {
+            float ba, br;
+            base_logprob_sums(eps, K, flat, ba, br);
+            base_a = ba; base_r = br;
         }
-        const double ent = (double)base_a / K - sh[1][0] / count + (double)base_r / (3.0 * K) - sh[0][0] / count;
+        const double ent = base_a / K - sh[1][0] / count + base_r / (3.0 * K) - sh[0][0] / count;
         out[0] = (float)ent;
     }
 }
@@ -1175,6 +1213,8 @@ static int max_blocks_per_cu(const void* fn, size_t lds, int threads) {
 template <int W, int MODE, bool TRAIN, int PREC, bool Q4 = false>
 static hipError_t launch_fwd_t(const FwdArgs& a, const NetTab& ht, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
     auto fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4>;
+    if constexpr (TRAIN)
+        if (a.flags & CFNERF_F_EPS_ROWS) fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4, true>;      // one latent row per ray / point
     const size_t lds = fwd_lds_bytes(W, ht.ha_sz, a.K);
     const int64_t units = (MODE == 0) ? a.N : (a.P + kTileM - 1) / kTileM;
     int grid = (int)std::min<int64_t>(units, (int64_t)n_cu * per_cu);
@@ -1210,12 +1250,16 @@ hipError_t launch_fused_fwd(const FwdArgs& a, const NetTab& ht, int mode, bool t
 template <int W>
 static hipError_t fwd_attrs_w(int ha, int* per_cu_out) {
     const size_t lds = fwd_lds_bytes(W, ha, kMaxK);      // the limit; a launch asks for what its K needs
-    const void* fns[10] = {
+    const void* fns[16] = {
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32, true>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_F32>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, false, PREC_F32>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_BF16X3>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3>),
-        reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, false, PREC_BF16X3>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_BF16X3>)};
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, false, PREC_BF16X3>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_BF16X3>),
+        // the latent-rows variants (CFNERF_F_EPS_ROWS)
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, true, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32, true, true>),
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32, false, true>),
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_BF16X3, false, true>)};
     int per_cu = 2;
     for (const void* fn : fns) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1243,10 +1287,10 @@ int fused_fwd_max_grid(int W, int ha, int n_cu) {
 
 hipError_t launch_entropy_finalize(const float* partials, int n_part, const float* flat, const float* eps, int K,
                                    double count, float* out, float* eps_keep, const float* rays, float* rays_keep, int64_t n_rays_floats,
-                                   hipStream_t st) {
+                                   int64_t n_eps_rows, int row_points, hipStream_t st) {
     const unsigned copy_blocks = (rays_keep != nullptr) ? (unsigned)((n_rays_floats + 255) / 256) : 0u;
     hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1 + copy_blocks), dim3(256), 0, st, partials, n_part, flat, eps, K, count, out, eps_keep,
-                       rays, rays_keep, rays_keep != nullptr ? n_rays_floats : 0);
+                       rays, rays_keep, rays_keep != nullptr ? n_rays_floats : 0, n_eps_rows, row_points);
     return hipGetLastError();
 }
 

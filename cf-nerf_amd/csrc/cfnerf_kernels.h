@@ -28,7 +28,7 @@ struct FwdArgs {
     const float* t_vals;      // [S]
     const float* t_rand;      // [N,S] or null
     const float* z_in;        // [N,S] explicit depths or null
-    const float* eps;         // [K,4]
+    const float* eps;         // [K,4]; CFNERF_F_EPS_ROWS: [N,K,4] per ray (ray mode) / [P,K,4] per point (points mode)
     const float* x;           // [P,90]         (points mode)
     int64_t N, P;             // rays, points (P = N*S in ray mode)
     int32_t S, K, flags;
@@ -55,9 +55,10 @@ struct FwdArgs {
 hipError_t launch_fused_fwd(const FwdArgs& a, const NetTab& host_tab, int mode, bool train, int prec, int n_cu, int per_cu, hipStream_t st, int* grid_out);
 hipError_t fused_fwd_set_attributes(int W, int ha, int* per_cu_out);      // per device, at model creation
 int fused_fwd_max_grid(int W, int ha, int n_cu);
+// n_eps_rows > 0: eps holds that many [K,4] rows (CFNERF_F_EPS_ROWS), each standing for `row_points` points of the launch
 hipError_t launch_entropy_finalize(const float* partials, int n_part, const float* flat, const float* eps, int K,
                                    double count, float* out, float* eps_keep, const float* rays, float* rays_keep, int64_t n_rays_floats,
-                                   hipStream_t st);
+                                   int64_t n_eps_rows, int row_points, hipStream_t st);
 hipError_t launch_composite(const float* raw, const float* z, const float* d, int64_t N, int S, int K, int wb,
                             float* rgb, float* disp, float* depth, float* weights, hipStream_t st);
 hipError_t launch_rays_setup(int H, int Wd, float focal, const RaysC2W& c2w, int use_c2w, const float* ro, const float* rd,

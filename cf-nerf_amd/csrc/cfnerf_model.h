@@ -78,6 +78,8 @@ struct Stash {
     bool points = false;            // ... in points mode (cfnerf_network_fwd: N = 1, S = P): differentiated by cfnerf_network_bwd
     bool q4 = false;                // ... with the trunk streams (h; then g_h, g_feat) in the Q4 layout (cfnerf_device.h): whole tiles, fp32
     uint64_t generation = 0;        // bumped by every STASH forward; cfnerf_render_bwd checks the caller's copy against it
+    const float* eps_rows = nullptr;    // CFNERF_F_EPS_ROWS forward: the CALLER's [N,K,4] / [P,K,4] latent rows (not copied: the
+                                        // caller keeps them alive until the backward, cfnerf.h); null: the launch's [K,4] in d_eps
 
     // binding
     char* base = nullptr; size_t cap = 0; bool owned = false;

@@ -171,6 +171,8 @@ void tail_bwd_kernel(const TailArgs A) {
     const int S = A.S, K = A.K;
     const int Kp = (K + A.ksplit - 1) / A.ksplit, k_lo = part * Kp, k_hi = min(K, k_lo + Kp);
     const float* rr = A.rays + ray * 11;
+    // CFNERF_F_EPS_ROWS: this ray's [K,4] latent row (one ray per wave: a uniform, scalar address)
+    const float* const eps_ray = (A.flags & CFNERF_F_EPS_ROWS) ? A.eps + (int64_t)__builtin_amdgcn_readfirstlane((int)ray) * (K * 4) : A.eps;
     const float dnorm = sqrtf((rr[3] * rr[3] + rr[4] * rr[4]) + rr[5] * rr[5]);
     const float cE = -((A.d_ent != nullptr) ? A.d_ent[0] : 0.f) / (float)((double)A.P * (double)K);
     const bool wb = (A.flags & CFNERF_F_WHITE_BKGD) != 0;
@@ -214,7 +216,7 @@ void tail_bwd_kernel(const TailArgs A) {
             // latent are scalar offsets, a lane keeps lane * 16 / lane * 8 (no 64-bit vector addresses in a kernel that lives at 256 registers)
             q.rv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(raw_rs, lane * 16, k * 1024, /*nt*/ 2));
             q.at = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(at_rs, lane * 8, k * 512, /*nt*/ 2));
-            q.e = *reinterpret_cast<const f32x4*>(A.eps + k * 4);
+            q.e = *reinterpret_cast<const f32x4*>(eps_ray + k * 4);
             q.G0 = A.d_rgb[ray * 3 * (int64_t)K + 0 * K + k]; q.G1 = A.d_rgb[ray * 3 * (int64_t)K + 1 * K + k];
             q.G2 = A.d_rgb[ray * 3 * (int64_t)K + 2 * K + k];
             q.Gd = (A.d_depth != nullptr) ? A.d_depth[ray * (int64_t)K + k] : 0.f;
@@ -287,9 +289,9 @@ void tail_bwd_kernel(const TailArgs A) {
 // flows_bwd_kernel: adjoint of the K flows + the entropy terms of NeRF_Flows.forward (MOD:225-291) given d loss / d raw [P,K,4].
 // lane = point; every latent of a point in one lane, so g_theta needs no partial sums.
 __global__ __launch_bounds__(kThreads)
-void flows_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ theta, const float* __restrict__ eps, const float* __restrict__ flat,
-                      const float* __restrict__ d_raw, const float* __restrict__ d_ent, int64_t P, int K, float* __restrict__ g_theta,
-                      float* __restrict__ gms_partials) {
+void flows_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ theta, const float* __restrict__ eps, int eps_rows,
+                      const float* __restrict__ flat, const float* __restrict__ d_raw, const float* __restrict__ d_ent, int64_t P, int K,
+                      float* __restrict__ g_theta, float* __restrict__ gms_partials) {
 #pragma clang fp contract(fast)
     const int lane = lane_id_opaque(), wave = wave_id();
     const int64_t pi = (int64_t)blockIdx.x * kThreads + wave * 64 + lane;
@@ -301,6 +303,7 @@ void flows_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ t
     const float r_std[3] = {flat[5], flat[6], flat[7]};
     float th[84], gms[8];
     GReg gth;
+    const float* const e_pt = eps_rows ? eps + p * K * 4 : eps;            // CFNERF_F_EPS_ROWS: this point's [K,4] row
     {
         const f32x4* tp = reinterpret_cast<const f32x4*>(theta + p * kThetaAll);
 #pragma unroll
@@ -315,7 +318,7 @@ void flows_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ t
         const f32x4 rv = *reinterpret_cast<const f32x4*>(raw + (((p >> 6) * K + k) * 64 + (p & 63)) * 4);    // tile-transposed stash: [tile p / 64][k][row p % 64][4]
         f32x4 g; g[0] = g[1] = g[2] = g[3] = 0.f;
         if (d_raw != nullptr) g = *reinterpret_cast<const f32x4*>(d_raw + (p * K + k) * 4);
-        const f32x4 e = *reinterpret_cast<const f32x4*>(eps + k * 4);
+        const f32x4 e = *reinterpret_cast<const f32x4*>(e_pt + k * 4);
         const float c0 = t_sigmoid(rv[0]), c1 = t_sigmoid(rv[1]), c2 = t_sigmoid(rv[2]), sg = t_sigmoid(rv[3]);
         float ga = g[3] + cE * (1.f - sg);                                     // + d(-mean(a - softplus a))  MOD:263
         float gz[3] = {g[0] + cE * (1.f - 2.f * c0), g[1] + cE * (1.f - 2.f * c1), g[2] + cE * (1.f - 2.f * c2)};   // MOD:278
@@ -339,11 +342,12 @@ hipError_t launch_tail_bwd(const TailArgs& ta, int64_t n_rays, int ksplit, hipSt
     return hipGetLastError();
 }
 
-hipError_t launch_flows_bwd(const float* raw, const float* theta, const float* eps, const float* flat, const float* d_raw, const float* d_ent,
-                            int64_t P, int K, float* g_theta, float* gms_partials, unsigned* grid_out, hipStream_t st) {
+hipError_t launch_flows_bwd(const float* raw, const float* theta, const float* eps, int eps_rows, const float* flat, const float* d_raw,
+                            const float* d_ent, int64_t P, int K, float* g_theta, float* gms_partials, unsigned* grid_out, hipStream_t st) {
     const unsigned grid = (unsigned)((P + kThreads - 1) / kThreads);
     if (grid_out) *grid_out = grid;
-    hipLaunchKernelGGL(flows_bwd_kernel, dim3(grid), dim3(kThreads), 0, st, raw, theta, eps, flat, d_raw, d_ent, P, K, g_theta, gms_partials);
+    hipLaunchKernelGGL(flows_bwd_kernel, dim3(grid), dim3(kThreads), 0, st, raw, theta, eps, eps_rows, flat, d_raw, d_ent, P, K, g_theta,
+                       gms_partials);
     return hipGetLastError();
 }
 

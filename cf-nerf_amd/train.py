@@ -16,7 +16,8 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .api import NeRF_Flows, _f32c, _pack_rays, _unwrap, t_vals_table
+from .api import (LATENT_DRAWS, NeRF_Flows, _draw_pairs, _f32c, _pack_rays, _unwrap, draw_train_randomness, netchunk_count,
+                  netchunk_eps_rows, t_vals_table)
 
 
 def backward_available() -> bool:
@@ -65,10 +66,19 @@ class Trainer:
     Latent samples: the reference draws eps once per forward call (MOD:234,246); here every rank must use the SAME eps in
     a step.  That is enforced, not assumed: rank 0 draws the latents of step t+1 and they travel in a 4*K-float tail of
     the step-t gradient all-reduce (the other ranks contribute zeros there), so no extra collective and no reliance on
-    identical seeding; step 0 uses one broadcast.  An explicit ``eps=`` argument overrides this (tests, benchmarks)."""
+    identical seeding; step 0 uses one broadcast.  An explicit ``eps=`` argument overrides this (tests, benchmarks): ``[K,4]`` for
+    the whole step or ``[N,K,4]``, one row per ray of this rank's shard.
+
+    ``latent_draws="netchunk"``: the reference's per-netchunk latents (api.draw_train_randomness).  A step draws the
+    ``C = netchunk_count(N_global, S, netchunk, chunk)`` latent pairs of the GLOBAL batch (on one process together with t_rand, in the
+    reference's order), every rank takes the rows of its own ray range (shard_bounds), and the ``C*K*4`` latents travel in the
+    all-reduce tail like the one set of the default mode.  ``eps_chunks=[C,K,4]`` gives them explicitly."""
 
     def __init__(self, net, lrate=5e-4, lrate_decay=250, beta1=0.0, world_size=1, group=None, start=0, force_allreduce=False,
-                 overlap_comm=False, time_comm=False, max_rays_per_launch=None):
+                 overlap_comm=False, time_comm=False, max_rays_per_launch=None, latent_draws="launch", netchunk=1024 * 64, chunk=1024 * 32):
+        if latent_draws not in LATENT_DRAWS:
+            raise ValueError(f"latent_draws must be one of {LATENT_DRAWS}, got {latent_draws!r}")
+        self.latent_draws, self.netchunk, self.chunk = latent_draws, int(netchunk), (int(chunk) if chunk else None)
         # max_rays_per_launch: a step's shard larger than this is walked in EQUAL slices (forward -> loss -> backward per slice, the
         # gradient accumulated by cfnerf_render_bwd_accumulate, ONE exchange and ONE Adam step at the end): the train-step workspace
         # is sized for a slice (3 MiB per ray at W = 256), not for the batch - the reference trains any N_rand (RUN:88-100,602)
@@ -99,6 +109,7 @@ class Trainer:
         self.entropy = torch.zeros(1, device=dev)
         self.t = 0
         self._buf_n = None
+        self._eps_rows = None           # this step's latent rows (netchunk mode): the stash reads them until the backward
 
     # ---- gradient exchange ---------------------------------------------------------------------------------------
     def _exchange_plan(self):
@@ -172,14 +183,33 @@ class Trainer:
             out.update(exposed_ms_mean=sum(ms) / len(ms), exposed_ms_max=max(ms), exposed_ms_min=min(ms), steps=len(ms))
         return out
 
+    def _n_latents(self):
+        """Shape of the latents one step exchanges: [K,4], or the [C,K,4] netchunk pairs of the current global batch."""
+        K = self.net.K_samples
+        return (K, 4) if self.latent_draws == "launch" else (self._n_chunks, K, 4)
+
+    def _draw(self):
+        if self.latent_draws == "launch":
+            return self.net.draw_eps()
+        return _draw_pairs(self._n_chunks, self.net.K_samples).pin_memory().to(self.net.flat.device, non_blocking=True)
+
+    def _tail(self, numel):
+        """The latents tail of the all-reduce buffer, grown (with the gradient view) when a netchunk step needs more than 4*MAX_K."""
+        n = self.net.n_params
+        if self.gbuf.numel() < n + numel:
+            self.gbuf = torch.zeros(n + numel, device=self.gbuf.device)
+            self.grad = self.gbuf[:n]
+            self._xplan = None
+        return self.gbuf[n:n + numel]
+
     def _step_eps(self):
         """Latents of the coming step, identical on every rank."""
         net = self.net
         if self.world == 1 and not self.force_allreduce:
-            return net.draw_eps()
-        if self._eps_next is None:                              # first step: one broadcast from rank 0
+            return self._draw()
+        if self._eps_next is None or tuple(self._eps_next.shape) != self._n_latents():    # first step: one broadcast from rank 0
             import torch.distributed as dist
-            eps = net.draw_eps() if self.rank == 0 else torch.zeros(net.K_samples, 4, device=net.flat.device)
+            eps = self._draw() if self.rank == 0 else torch.zeros(*self._n_latents(), device=net.flat.device)
             if eps.is_cuda and dist.get_backend(self.group) == "gloo":
                 host = eps.cpu()
                 dist.broadcast(host, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
@@ -191,16 +221,23 @@ class Trainer:
 
     def _queue_next_eps(self):
         """Before the all-reduce: rank 0 writes the NEXT step's latents behind the gradient, everyone else zeros."""
-        K, n = self.net.K_samples, self.net.n_params
-        tail = self.gbuf[n:n + 4 * K]
+        shape = self._n_latents()
+        numel = 1
+        for d in shape:
+            numel *= d
+        tail = self._tail(numel)
         if self.rank == 0:
-            tail.copy_(self.net.draw_eps().reshape(-1))      # pinned, non-blocking: the host keeps running ahead
+            tail.copy_(self._draw().reshape(-1))             # pinned, non-blocking: the host keeps running ahead
         else:
             tail.zero_()
 
     def _take_next_eps(self):
-        K, n = self.net.K_samples, self.net.n_params
-        self._eps_next = self.gbuf[n:n + 4 * K].reshape(K, 4).clone()
+        shape = self._n_latents()
+        n = self.net.n_params
+        numel = 1
+        for d in shape:
+            numel *= d
+        self._eps_next = self.gbuf[n:n + numel].reshape(shape).clone()
 
     def _buffers(self, N, K):
         if self._buf_n != (N, K):
@@ -221,6 +258,10 @@ class Trainer:
         net, lib, st = self.net, L.lib(), L.stream()
         rows = lambda t: t[a:b] if t is not None else None
         n, K = b - a, net.K_samples
+        if eps.dim() == 3:                  # one latent row per ray (CFNERF_F_EPS_ROWS): the slice's rows
+            if eps.shape[0] != self.packed.shape[0]:
+                raise ValueError(f"latent rows for {eps.shape[0]} rays, the shard has {self.packed.shape[0]}")
+            eps, flags = eps[a:b], flags | L.F_EPS_ROWS
         L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed[a:b]), L.ptr(t_vals), L.ptr(rows(t_rand)), L.ptr(rows(z_vals)), L.ptr(eps),
                                       n, S, K, flags | (L.F_STASH if grad is not None else 0), L.ptr(self.rgb_map[a:b]), L.ptr(self.disp[a:b]),
                                       L.ptr(self.depth[a:b]), None, L.ptr(rows(weights)), None, None, L.ptr(entropy), st), "cfnerf_render_fwd")
@@ -234,7 +275,7 @@ class Trainer:
                 "cfnerf_render_bwd_accumulate" if accumulate else "cfnerf_render_bwd")
 
     def forward_backward(self, H, W, focal, rays, target, t_rand=None, eps=None, near=0., far=1., ndc=True,
-                         lindisp=False, white_bkgd=False, perturb=1., t_vals=None, **_ignored):
+                         lindisp=False, white_bkgd=False, perturb=1., t_vals=None, eps_chunks=None, **_ignored):
         """Forward + loss + backward of this rank's shard.  Leaves the (un-reduced) gradient in ``self.grad``."""
         net = self.net
         dev = net.flat.device
@@ -243,17 +284,33 @@ class Trainer:
         S = t_vals.shape[0]
         self._buffers(N, K)
         _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far, out=self.packed)
+        if self.latent_draws == "netchunk" and eps is None:
+            # the GLOBAL batch's per-netchunk pairs, expanded to ray rows; this rank takes its own range (the union of the shards is the
+            # one-process batch).  One process drawing implicitly: t_rand and the pairs in the reference's order
+            Ng = N * self.world
+            if eps_chunks is None:
+                if self.world == 1 and not self.force_allreduce:
+                    tr, eps_chunks = draw_train_randomness(Ng, S, K, self.chunk, self.netchunk, perturb)
+                    t_rand = tr.to(dev) if t_rand is None else t_rand
+                else:
+                    raise RuntimeError("netchunk latents of a sharded step come from Trainer.step (or pass eps_chunks=)")
+            a, b = self.rank * N, (self.rank + 1) * N
+            self.last_eps_chunks = eps_chunks                               # (the step's pairs: identical on every rank)
+            eps = netchunk_eps_rows(_f32c(eps_chunks).to(dev), Ng, S, self.netchunk, self.chunk)[a:b]
         if perturb > 0. and t_rand is None:
             t_rand = torch.rand(N, S, device=dev)
         if perturb <= 0.:
             t_rand = None
         if eps is None:
             eps = net.draw_eps()
-        eps = _f32c(eps)
+        eps = _f32c(eps).to(dev)
+        if eps.dim() == 3 and eps.shape[0] != N:
+            raise ValueError(f"latent rows for {eps.shape[0]} rays, the shard has {N}")
+        self._eps_rows = eps if eps.dim() == 3 else None
         net._sync()
         flags = L.F_TRAIN | (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
         n_sl = self.n_slices(N)
-        t_rand = _f32c(t_rand) if t_rand is not None else None
+        t_rand = _f32c(t_rand).to(dev) if t_rand is not None else None
         target = _f32c(target)
         # the shard in n_sl equal slices: every loss term is taken with n_total = the FULL batch and beta1 / (world n_sl) on the slice's
         # entropy (equal slices: the mean of the slice means is the batch mean), so the slice gradients and the scalar contributions ADD.
@@ -293,8 +350,13 @@ class Trainer:
     def _step(self, forward_backward, exchange, H, W, focal, rays, target, kw):
         """Body of step / step_hierarchical: the step's latents, forward + backward, the gradient exchange, Adam, re-pack."""
         dist_on = self.world > 1 or self.force_allreduce
-        if kw.get("eps") is None and dist_on:
-            kw["eps"] = self._step_eps()
+        if self.latent_draws == "netchunk":
+            S = (kw.get("t_vals").shape[0] if kw.get("t_vals") is not None else t_vals_table().shape[0])
+            self._n_chunks = netchunk_count(rays[1].reshape(-1, 3).shape[0] * self.world, S, self.netchunk, self.chunk)
+            if dist_on:
+                self._tail(self._n_chunks * self.net.K_samples * 4)       # (grown BEFORE the backward writes the gradient view)
+        if kw.get("eps") is None and kw.get("eps_chunks") is None and dist_on:
+            kw["eps_chunks" if self.latent_draws == "netchunk" else "eps"] = self._step_eps()
         forward_backward(H, W, focal, rays, target, **kw)
         if dist_on:
             self._queue_next_eps()
@@ -312,7 +374,8 @@ class Trainer:
 
     def step(self, H, W, focal, rays, target, **kw):
         """One full train step.  Returns the device tensor [loss, loss_nll, mse, psnr] of the local shard."""
-        kw = {k: v for k, v in kw.items() if k in ("t_rand", "eps", "near", "far", "ndc", "lindisp", "white_bkgd", "perturb", "t_vals")}
+        kw = {k: v for k, v in kw.items() if k in ("t_rand", "eps", "eps_chunks", "near", "far", "ndc", "lindisp", "white_bkgd", "perturb",
+                                                     "t_vals")}
         return self._step(self.forward_backward, self._exchange, H, W, focal, rays, target, kw)
 
     # ---- EXTENSION (not in the reference, SURVEY R1 / 8f-4): coarse + fine sampling through the single network -----
@@ -324,6 +387,8 @@ class Trainer:
         ``coarse_loss`` the coarse pass keeps a stash and its own loss term is differentiated too
         (nerf-pytorch adds img2mse(rgb0); here the same KDE-NLL as the fine term), so ``self.grad`` is the gradient of
         loss_fine + loss_coarse.  Returns it; ``self.scalars`` holds the fine pass's [loss, nll, mse, psnr]."""
+        if self.latent_draws == "netchunk":
+            raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
         net = self.net
         dev = net.flat.device
         N, K, S, Ni = rays[1].reshape(-1, 3).shape[0], net.K_samples, int(N_samples), int(N_importance)
@@ -362,6 +427,8 @@ class Trainer:
 
     def step_hierarchical(self, H, W, focal, rays, target, **kw):
         """One full train step of the coarse + fine EXTENSION (see forward_backward_hierarchical)."""
+        if self.latent_draws == "netchunk":
+            raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
         # always the plain one-bucket all-reduce: this gradient is grad_fine + grad_c, added by torch after the last backward, while
         # the early-range event that overlap_comm's first bucket waits for fires inside that backward, before the add
         return self._step(self.forward_backward_hierarchical, lambda: allreduce_sum_(self.gbuf, self.world, self.group, self.force_allreduce),

@@ -79,8 +79,15 @@ enum {
     CFNERF_F_TRAIN      = 1 << 0,       /* train branch of NeRF_Flows.forward (MOD:225-291): log-dets + entropy */
     CFNERF_F_LINDISP    = 1 << 1,       /* render_rays(lindisp=True)  RUN:513-514 */
     CFNERF_F_WHITE_BKGD = 1 << 2,       /* raw2outputs(white_bkgd=True) RUN:451-452 */
-    CFNERF_F_STASH      = 1 << 3        /* keep activations for cfnerf_render_bwd (implies TRAIN); ONE stash per model: a later
+    CFNERF_F_STASH      = 1 << 3,       /* keep activations for cfnerf_render_bwd (implies TRAIN); ONE stash per model: a later
                                            STASH forward replaces it and bumps cfnerf_model_stash_generation */
+    CFNERF_F_EPS_ROWS   = 1 << 4        /* eps holds one [K,4] row per work item - per RAY in cfnerf_render_fwd ([N,K,4]), per POINT
+                                           in cfnerf_network_fwd ([P,K,4]) - instead of one [K,4] for the launch: the reference draws
+                                           fresh latents per netchunk (RUN:47-64,82; MOD:234,246), so a batch of several netchunks
+                                           uses several latent sets.  Train branch only (cfnerf_render_eval refuses it).  With
+                                           CFNERF_F_STASH the stash keeps the CALLER's eps pointer (no copy, no workspace growth):
+                                           the rows buffer must stay alive and unchanged until the matching backward has been
+                                           enqueued and has run, like a lent workspace */
 };
 
 CFNERF_API int         cfnerf_version(void);
@@ -137,12 +144,14 @@ CFNERF_API int cfnerf_sample_points(const float* rays, const float* t_vals, cons
  *   rays    [N,11]          t_vals [S]            t_rand [N,S] or NULL (perturb == 0)
  *   z_vals_opt [N,S] or NULL: explicit sample depths per ray (then t_vals / t_rand are not read) - used by the
  *                     hierarchical-sampling EXTENSION below, which the reference does not have
- *   eps     [K,4] = (eps_rgb0, eps_rgb1, eps_rgb2, eps_alpha) per latent sample (MOD:234,246 / 198,204)
+ *   eps     [K,4] = (eps_rgb0, eps_rgb1, eps_rgb2, eps_alpha) per latent sample (MOD:234,246 / 198,204);
+ *           with CFNERF_F_EPS_ROWS [N,K,4]: row i holds the latents of ray i
  *   rgb_map [N,3,K]  disp_map [N,K]  depth_map [N,K]           (written unless all three are NULL and kstats is given)
  *   raw_opt [N,S,K,4], weights_opt [N,S,K], pts_opt [N,S,3]    (NULL = not wanted)
  *   kstats_opt [N,8]  fused reductions over the K latent samples, what the evaluation loop derives from the
  *                     per-K maps at RUN:1122-1131: mean_K rgb (3) | np.std_K(rgb) * n/(n-1) (3) | mean_K disp | mean_K depth
- *   entropy_out [1]   loss_entropy of MOD:286 (TRAIN only, may be NULL otherwise)                */
+ *   entropy_out [1]   loss_entropy of MOD:286 (TRAIN only, may be NULL otherwise); with CFNERF_F_EPS_ROWS the point-weighted
+ *                     mean over the launch (= the mean of the reference's per-netchunk values weighted by their points) */
 CFNERF_API int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, const float* t_rand,
                       const float* z_vals_opt, const float* eps, int64_t N, int S, int K, int flags,
                       float* rgb_map, float* disp_map, float* depth_map,
@@ -153,7 +162,7 @@ CFNERF_API int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float
  * RUN:1117-1131: K-mean prediction, np.std * n/(n-1) uncertainty, mean disparity / depth) and the per-pixel integrand of
  * img2mse(rgb_mean, target) (RUN:1028, HLP:15), all reduced INSIDE the fused forward: only 32 (+12) bytes per pixel leave
  * the chip instead of 20*K.  Eval branch (fixed eps, no jitter).  kstats [N,8] as in cfnerf_render_fwd; gt_opt [N,3] and
- * sqerr_opt [N,3] = (K-mean rgb - gt)^2 go together or are both NULL.                                                  */
+ * sqerr_opt [N,3] = (K-mean rgb - gt)^2 go together or are both NULL.  eps is always [K,4]: CFNERF_F_EPS_ROWS is refused. */
 CFNERF_API int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, const float* eps, int64_t N, int S, int K,
                        int flags, const float* gt_opt, float* kstats, float* sqerr_opt, cfnerf_stream s);
 
@@ -168,7 +177,8 @@ CFNERF_API int cfnerf_sample_pdf(const float* rays, const float* t_vals, const f
 /* replaces: NeRF_Flows.forward(x, is_val, is_test) MOD:188-291 on pre-embedded inputs x [P,90]
  * (what batchify()/run_network hand to the model, RUN:47-64,82).  raw [P,K,4].  With CFNERF_F_STASH (implies TRAIN) the
  * activations are kept for cfnerf_network_bwd (the model's ONE stash, bound as one "ray" of P samples: size the workspace
- * with cfnerf_workspace_bytes(cfg, 1, P, K)).                                                     */
+ * with cfnerf_workspace_bytes(cfg, 1, P, K)).  eps [K,4]; with CFNERF_F_EPS_ROWS [P,K,4], one row per point (the
+ * reference's netchunk boundaries are point boundaries).                                          */
 CFNERF_API int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_t P, int K, int flags,
                        float* raw, float* entropy_out, cfnerf_stream s);
 
@@ -206,7 +216,8 @@ CFNERF_API uint64_t cfnerf_model_stash_generation(const cfnerf_model* m);
  * of the cfnerf_render_fwd(... CFNERF_F_STASH ...) whose generation is `stash_generation`; if a later STASH forward
  * has replaced that stash the call fails (CFNERF_E_INVALID) instead of differentiating the wrong batch.
  * d_depth_map may be NULL.  d_entropy points to ONE device float, d(loss)/d(loss_entropy) (e.g. beta1); NULL
- * means 0.  grad_flat [param_count] is OVERWRITTEN with the gradient in the flat parameter layout.             */
+ * means 0.  grad_flat [param_count] is OVERWRITTEN with the gradient in the flat parameter layout.  A CFNERF_F_EPS_ROWS
+ * forward is differentiated with its per-ray rows, read from the caller's eps buffer (see CFNERF_F_EPS_ROWS).  */
 CFNERF_API int cfnerf_render_bwd(cfnerf_model* m, uint64_t stash_generation, const float* d_rgb_map, const float* d_depth_map,
                       const float* d_entropy, float* grad_flat, cfnerf_stream s);
 /* replaces: the same loss.backward() when ONE optimiser step's batch is walked in slices (the reference renders any N_rand and any
