@@ -15,13 +15,10 @@ raises if the library is missing or the tensors are not on a GPU.
 
 Extra (new) keyword arguments make the reference's hidden randomness explicit:
 ``t_rand [N,S]``, ``eps_alpha [K,1]``, ``eps_rgb [K,3]``.  When left ``None`` they are drawn with
-torch in the reference's order (RUN:524 -> MOD:234 -> MOD:246).
-
-Reference-exact latents (opt-in, ``create_nerf`` with ``args.latent_draws = "netchunk"``): the reference draws a fresh
-latent pair per ``netchunk`` points (RUN:47-64,82; MOD:234,246), so a train batch larger than one netchunk uses several
-latent sets.  In that mode the train branch draws them in the reference's order (``draw_train_randomness``), lays them
-out as one row per ray (``netchunk_eps_rows``) and launches with ``CFNERF_F_EPS_ROWS``; explicit latents are then
-``eps_alpha [C,K,1]`` / ``eps_rgb [C,K,3]``, one pair per netchunk.
+torch in the reference's order.  ``latents.py`` is the one description of that order, of the ``[K,4]`` layout and of the
+reference-exact per-netchunk latents (opt-in, ``create_nerf`` with ``args.latent_draws = "netchunk"``; explicit latents are then
+``eps_alpha [C,K,1]`` / ``eps_rgb [C,K,3]``, one pair per netchunk); every train launch here takes its latents from
+``latents.train_latents``.
 """
 from __future__ import annotations
 
@@ -33,6 +30,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import latents as LT
+from .latents import LATENT_DRAWS, draw_train_randomness, netchunk_count, netchunk_eps_point_rows, netchunk_eps_rows    # noqa: F401  (public here too)
 
 # --------------------------------------------------------------------------------------------
 # misc helpers (HLP:15-16)
@@ -261,92 +260,13 @@ def reference_init(shapes, netdepth, K_samples=None):
 
 
 # --------------------------------------------------------------------------------------------
-# per-netchunk latents (the reference's batchify_rays -> run_network -> batchify nesting, RUN:47-64,82,88-100)
-LATENT_DRAWS = ("launch", "netchunk")
-
-
-def _ray_cuts(N, chunk):
-    """(first ray, rays) of every batchify_rays cut of an N-ray batch (RUN:88-100); ``chunk=None``: one cut."""
-    step = N if not chunk else int(chunk)
-    return [(r0, min(step, N - r0)) for r0 in range(0, N, max(step, 1))]
-
-
-def netchunk_count(N, S, netchunk, chunk=None):
-    """Latent pairs the reference draws for an N-ray train batch of S samples per ray: every ``chunk``-ray cut restarts
-    batchify's count and makes ``ceil(n_c * S / netchunk)`` network calls."""
-    return sum(-(-(n * S) // int(netchunk)) for _, n in _ray_cuts(N, chunk))
-
-
-def netchunk_eps_rows(eps_chunks, N, S, netchunk, chunk=None):
-    """Expand per-netchunk latents ``eps_chunks [C,K,4]`` (in draw order) to ray rows ``[N,K,4]``: ray i gets the latents of
-    the network call that evaluates its points.  Needs ``netchunk % S == 0`` (else the reference switches latents in the
-    middle of a ray, which one row per ray cannot express)."""
-    netchunk, S = int(netchunk), int(S)
-    if netchunk % S:
-        raise NotImplementedError(f"netchunk ({netchunk}) is not a multiple of the samples per ray ({S}): the reference then changes "
-                                  f"latents in the middle of a ray, which per-ray latent rows cannot express")
-    per = netchunk // S                          # rays of one network call
-    idx, base = [], 0
-    for _, n in _ray_cuts(N, chunk):
-        idx.append(base + torch.arange(n) // per)
-        base += -(-(n * S) // netchunk)
-    if eps_chunks.shape[0] != base:
-        raise ValueError(f"{eps_chunks.shape[0]} latent pairs given; N={N}, S={S}, netchunk={netchunk}, chunk={chunk} needs {base}")
-    idx = torch.cat(idx) if idx else torch.zeros(0, dtype=torch.long)
-    return eps_chunks.index_select(0, idx.to(eps_chunks.device)).contiguous()
-
-
-def netchunk_eps_point_rows(eps_chunks, P, netchunk):
-    """Per-netchunk latents ``[C,K,4]`` as one row per point ``[P,K,4]`` (batchify over P points, RUN:47-64)."""
-    idx = torch.arange(int(P)) // int(netchunk)
-    if eps_chunks.shape[0] != -(-int(P) // int(netchunk)):
-        raise ValueError(f"{eps_chunks.shape[0]} latent pairs given; P={P}, netchunk={netchunk} needs {-(-int(P) // int(netchunk))}")
-    return eps_chunks.index_select(0, idx.to(eps_chunks.device)).contiguous()
-
-
-def _draw_pairs(n, K):
-    """n latent pairs from torch's CPU generator, eps_alpha then eps_rgb per network call (MOD:234,246), as ``[n,K,4]``."""
-    out = torch.empty(n, K, 4)
-    for c in range(n):
-        ea = torch.empty([K, 1]).normal_()
-        er = torch.empty([K, 3]).normal_()
-        out[c, :, :3], out[c, :, 3:] = er, ea
-    return out
-
-
-def draw_train_randomness(N, S, K, chunk, netchunk, perturb, raw_noise_std=0.):
-    """The randomness of one reference train render of N rays, from torch's CPU generator in the reference's order.  Per
-    ``chunk``-ray cut (RUN:88-100): ``t_rand [n_c,S]`` if ``perturb > 0`` (RUN:524), then per network call of the cut
-    eps_alpha, eps_rgb (MOD:234,246), then - if ``raw_noise_std > 0`` - the ``randn([n_c,S,K])`` raw2outputs draws and never
-    uses (RUN:434).  Returns ``(t_rand [N,S] or None, eps_chunks [C,K,4])``."""
-    netchunk = int(netchunk)
-    tr, eps = [], []
-    for _, n in _ray_cuts(N, chunk):
-        if perturb > 0.:
-            tr.append(torch.rand([n, S]))
-        eps.append(_draw_pairs(-(-(n * S) // netchunk), K))
-        if raw_noise_std > 0.:
-            torch.randn([n, S, K])
-    t_rand = (torch.cat(tr, 0) if tr else torch.zeros(0, S)) if perturb > 0. else None
-    return t_rand, (torch.cat(eps, 0) if eps else torch.zeros(0, K, 4))
-
-
-def _per_netchunk_latents(eps_alpha, eps_rgb):
-    """True for explicit per-netchunk latents ``eps_alpha [C,K,1]`` / ``eps_rgb [C,K,3]``, False for one ``[K,1]`` / ``[K,3]`` set or none."""
-    if eps_alpha is None and eps_rgb is None:
-        return False
-    if eps_alpha is None or eps_rgb is None or eps_alpha.dim() != eps_rgb.dim() or eps_alpha.dim() not in (2, 3):
-        raise ValueError("eps_alpha and eps_rgb go together: [K,1] / [K,3] (one set) or [C,K,1] / [C,K,3] (one pair per netchunk)")
-    return eps_alpha.dim() == 3
-
-
-def _latents(model, eps_alpha, eps_rgb, train, device):
-    """[K,4] latents of a launch: the explicit ``eps_rgb | eps_alpha`` when given, else fresh train draws or the fixed eval ones."""
-    if _per_netchunk_latents(eps_alpha, eps_rgb):
+def _latents(model, explicit, train, device):
+    """[K,4] latents of a launch that takes ONE set: the packed explicit one when given, else fresh train draws or the fixed eval ones."""
+    if explicit is not None and explicit.dim() == 3:
         raise ValueError("per-netchunk latents [C,K,1] / [C,K,3] cannot be one launch's [K,4] set (train branch of render_rays / "
-                         "NeRF_Flows.forward only)")
-    if eps_alpha is not None or eps_rgb is not None:
-        return torch.cat([eps_rgb, eps_alpha], -1).to(device, torch.float32).contiguous()
+                         "NeRF_Flows.forward only; the eval branch uses the fixed latents)")
+    if explicit is not None:
+        return explicit.to(device).contiguous()
     return model.draw_eps() if train else model.eval_eps()
 
 
@@ -398,7 +318,7 @@ class NeRF_Flows(nn.Module):
         L.check(L.lib().cfnerf_model_create(C.byref(self.cfg), C.byref(h)), "cfnerf_model_create")
         self._h = h
         self._packed_version = None
-        self._next_eps = None          # explicit latents handed from render_rays to an unfused network_query_fn
+        self._next_eps = None          # the launch's latents, handed from render_rays through an unfused network_query_fn to forward()
         self.latent_draws = "launch"   # "netchunk": per-netchunk train latents like the reference (create_nerf: args.latent_draws)
         self.netchunk = 1024 * 64      # points per network call of the reference (netchunk_per_gpu * n_gpus, RUN:82,384)
         self._ws = None                # train-step workspace: a torch-owned block lent to the library
@@ -528,18 +448,22 @@ class NeRF_Flows(nn.Module):
         # the device copy is rebuilt only when the (plain-attribute) latents were replaced or edited in place
         key = (id(self.sample_rgb), self.sample_rgb._version, id(self.sample_alpha), self.sample_alpha._version)
         if getattr(self, "_eval_eps_key", None) != key:
-            e = torch.cat([self.sample_rgb, self.sample_alpha], -1).to(torch.float32).clone()
+            e = LT.pack(self.sample_alpha, self.sample_rgb)
             e[-1] = 0
             self._eval_eps_dev, self._eval_eps_key = e.to(self.device), key
         return self._eval_eps_dev
 
     def draw_eps(self):
-        """Fresh train latents in the reference's order: eps_alpha then eps_rgb (MOD:234,246), drawn from torch's CPU
-        generator like the reference.  The copy to the device goes through pinned memory and does not block the host
-        (a pageable copy would stall the launch queue every step)."""
-        ea = torch.empty([self.K_samples, 1]).normal_()
-        er = torch.empty([self.K_samples, 3]).normal_()
-        return torch.cat([er, ea], -1).pin_memory().to(self.device, non_blocking=True)
+        """One fresh train pair ``[K,4]`` on the device (latents.draw_pairs: the reference's order; the upload does not block the host)."""
+        return LT.to_device(LT.draw_pairs(1, self.K_samples)[0], self.device)
+
+    def _one_call_only(self, is_test):
+        """True when a batch of points must reach forward() in ONE call, not in batchify's chunks."""
+        if torch.is_grad_enabled() and self.flat.requires_grad and not is_test:
+            # one launch = the model's one stash; chunks would each replace it and the backward would re-run their forwards
+            return True
+        # latent rows of the whole batch (render_rays' hand-over): its network calls are already in them
+        return self._next_eps is not None and self._next_eps.dim() == 3
 
     # ---- forward (MOD:188-291) ---------------------------------------------------------------
     def forward(self, x, is_val=False, is_test=False, eps_alpha=None, eps_rgb=None):
@@ -549,21 +473,16 @@ class NeRF_Flows(nn.Module):
         self._sync()
         xf = _f32c(x.reshape(-1, x.shape[-1]))
         P, K = xf.shape[0], self.K_samples
-        if self._next_eps is not None and eps_alpha is None and eps_rgb is None:
+        explicit = LT.pack(eps_alpha, eps_rgb)
+        if self._next_eps is not None and explicit is None:
             eps = self._next_eps                                    # latents chosen by the enclosing render_rays call
-        elif not is_test and (self.latent_draws == "netchunk" or _per_netchunk_latents(eps_alpha, eps_rgb)):
-            # per-netchunk latents (batchify, RUN:47-64): explicit [C,K,1] / [C,K,3] or C fresh pairs, one row per point
-            if eps_alpha is not None or eps_rgb is not None:
-                chunks = torch.cat([eps_rgb, eps_alpha], -1).to(torch.float32)
-            else:
-                chunks = _draw_pairs(-(-P // self.netchunk), K)
-            eps = netchunk_eps_point_rows(chunks, P, self.netchunk).to(self.device)
-        else:
-            eps = _latents(self, eps_alpha, eps_rgb, not is_test, self.device)
-        if eps.dim() == 3 and eps.shape[0] != P:
-            # (point rows from render_rays cover the whole batch: a network_query_fn of its own must hand all of it to ONE call)
-            raise ValueError(f"latent rows for {eps.shape[0]} points, the call has {P}: in netchunk mode render_rays hands one latent row "
-                             f"per point of the whole batch, so a custom network_query_fn must evaluate all of them in one NeRF_Flows call")
+        elif is_test:
+            eps = _latents(self, explicit, False, self.device)
+        else:                                                       # P points = P rays of one sample (batchify, RUN:47-64)
+            eps = LT.to_device(LT.train_latents(self.latent_draws, explicit, N=P, S=1, K=K, netchunk=self.netchunk)[1], self.device)
+        # (point rows from render_rays cover the whole batch: a network_query_fn of its own must hand all of it to ONE call)
+        LT.check_rows(eps, P, "points", hint=": in netchunk mode render_rays hands one latent row per point of the whole batch, so a custom "
+                                             "network_query_fn must evaluate all of them in one NeRF_Flows call")
         if torch.is_grad_enabled() and self.flat.requires_grad and not is_test and P > 0:
             # the reference's forward is an autograd graph (MOD:188-291): so is this one - cfnerf_network_fwd with the
             # activation stash, differentiated by cfnerf_network_bwd (gradients reach the parameters; x is a constant)
@@ -593,13 +512,19 @@ def _params_token(model):
     return (model.flat._version, model.params_serial)
 
 
-def _refuse_changed_params(model, token, pack_serial):
+def _mark_forward(ctx, model):
+    """What a backward must meet again (``_check_backward``): its forward's stash generation, weights and the library's packed copy of them."""
+    ctx.generation = L.lib().cfnerf_model_stash_generation(model.handle)
+    ctx.params_at, ctx.pack_serial = _params_token(model), model.pack_serial
+
+
+def _check_backward(ctx, model, packed=True):
     """A backward differentiates the stashed activations of ITS forward against what the library holds NOW: the packed weights AND -
     for the base Gaussians (alpha_mean / alpha_std / rgb_mean / rgb_std) - the flat parameter buffer itself, which the flow-adjoint
     kernels read live.  If either changed since the forward (optimizer.step(), Trainer.step() through the same handle,
     load_state_dict(), mark_dirty(); or a re-pack by a later launch) the result would be silently inconsistent whether or not the
     activation stash is still the forward's (round-4 advisor) - torch autograd raises in this situation, so do we."""
-    if _params_token(model) != token or model.pack_serial != pack_serial:
+    if _params_token(model) != ctx.params_at or (packed and model.pack_serial != ctx.pack_serial):
         raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: the "
                            "parameters of NeRF_Flows changed between this forward and its backward (call backward() before "
                            "optimizer.step() / Trainer.step() / load_state_dict())")
@@ -608,9 +533,7 @@ def _refuse_changed_params(model, token, pack_serial):
 def _network_fwd(model, xf, eps, K, flags):
     """cfnerf_network_fwd of the encoded points ``xf [P,90]`` into new ``raw [P,K,4]`` and a zeroed entropy accumulator ``[1]``.
     ``eps`` is the launch's ``[K,4]`` or one row per point ``[P,K,4]`` (CFNERF_F_EPS_ROWS)."""
-    if eps.dim() == 3:
-        if eps.shape[0] != xf.shape[0]:
-            raise ValueError(f"latent rows for {eps.shape[0]} points, the launch has {xf.shape[0]}")
+    if LT.check_rows(eps, xf.shape[0], "points"):
         flags |= L.F_EPS_ROWS
     raw = torch.empty(xf.shape[0], K, 4, device=xf.device)
     ent = torch.zeros(1, device=xf.device)
@@ -629,29 +552,26 @@ class _NetworkFn(torch.autograd.Function):
     def _forward_stash(model, xf, eps):
         K = eps.shape[-2]
         model.ensure_workspace(1, xf.shape[0], K)
-        raw, ent = _network_fwd(model, xf, eps, K, L.F_TRAIN | L.F_STASH)
-        return raw, ent, L.lib().cfnerf_model_stash_generation(model.handle)
+        return _network_fwd(model, xf, eps, K, L.F_TRAIN | L.F_STASH)
 
     @staticmethod
     def forward(ctx, flat, model, xf, eps):
-        raw, ent, ctx.generation = _NetworkFn._forward_stash(model, xf, eps)
+        raw, ent = _NetworkFn._forward_stash(model, xf, eps)
         ctx.model, ctx.xf, ctx.eps, ctx.n_params = model, xf, eps, flat.numel()
-        ctx.params_at = _params_token(model)                       # the weights this graph was taken at
-        ctx.pack_serial = model.pack_serial                        # ... and the packed copy of them the library held
+        _mark_forward(ctx, model)
         return raw, ent.reshape(())
 
     @staticmethod
     def backward(ctx, d_raw, d_ent):
         model, lib = ctx.model, L.lib()
-        if _params_token(model) != ctx.params_at or getattr(model, "_dirty", False):
-            _refuse_changed_params(model, None, None)              # (always raises)
-        if lib.cfnerf_model_stash_generation(model.handle) == ctx.generation:
-            _refuse_changed_params(model, ctx.params_at, ctx.pack_serial)      # the stash is this forward's: so must the packed weights be
-        else:
+        stash_kept = lib.cfnerf_model_stash_generation(model.handle) == ctx.generation
+        _check_backward(ctx, model, packed=stash_kept)             # the stash is this forward's: so must the packed weights be
+        if not stash_kept:
             # the stash is gone (a later grad-enabled forward replaced it): re-run the forward - the SAME forward, the parameters being the
             # ones it was taken at (checked above; a re-pack of unchanged parameters in between is harmless here)
             model._sync()
-            ctx.generation = _NetworkFn._forward_stash(model, ctx.xf, ctx.eps)[2]
+            _NetworkFn._forward_stash(model, ctx.xf, ctx.eps)
+            ctx.generation = lib.cfnerf_model_stash_generation(model.handle)
         grad = torch.empty(ctx.n_params, device=model.flat.device)
         dr = _f32c(d_raw) if d_raw is not None else None
         de = _f32c(d_ent.reshape(1)) if d_ent is not None else None
@@ -726,11 +646,8 @@ def batchify(fn, chunk):
 
     def ret(inputs, is_val, is_test):
         m = getattr(fn, "module", fn)
-        if isinstance(m, NeRF_Flows) and torch.is_grad_enabled() and m.flat.requires_grad and not is_test:
-            # one launch = the model's one stash; chunks would each replace it and the backward would re-run their forwards
+        if isinstance(m, NeRF_Flows) and m._one_call_only(is_test):
             return fn(inputs, is_val, is_test)
-        if isinstance(m, NeRF_Flows) and m._next_eps is not None and m._next_eps.dim() == 3:
-            return fn(inputs, is_val, is_test)          # latent rows of the whole batch: its network calls are already in them
         A, B = [], []
         for i in range(0, inputs.shape[0], chunk):
             a, b = fn(inputs[i:i + chunk], is_val, is_test)
@@ -771,9 +688,7 @@ def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True,
     zeroed accumulator ``entropy [1]``; an output that was not asked for is None.  S is that of ``z_vals [N,S]`` (explicit depths,
     which the library then prefers to ``t_rand``) or of the sample table ``t_vals``."""
     N, K = rays.shape[0], eps.shape[-2]
-    if eps.dim() == 3:                   # one [K,4] row per ray (CFNERF_F_EPS_ROWS): the kernels read row i for ray i, so exactly N rows
-        if eps.shape[0] != N:
-            raise ValueError(f"latent rows for {eps.shape[0]} rays, the launch has {N} (per-netchunk latents go through netchunk_eps_rows)")
+    if LT.check_rows(eps, N, "rays"):
         flags |= L.F_EPS_ROWS
     S = z_vals.shape[1] if z_vals is not None else t_vals.shape[0]
     dev = rays.device
@@ -798,8 +713,7 @@ class _RenderFn(torch.autograd.Function):
         ctx.model = model
         ctx.eps = eps               # latent rows: the stash reads the caller's buffer until the backward (cfnerf.h, CFNERF_F_EPS_ROWS)
         ctx.n_params = flat.numel()
-        ctx.generation = L.lib().cfnerf_model_stash_generation(model.handle)
-        ctx.params_at, ctx.pack_serial = _params_token(model), model.pack_serial
+        _mark_forward(ctx, model)
         ctx.shape = (N, 3, K)
         pts = o['pts'] if want_pts else torch.empty(0, device=rays.device)
         # (torch keeps only the LAST mark_non_differentiable call's tensors: pts alone, as before; the backward ignores d_disp / d_raw)
@@ -809,7 +723,7 @@ class _RenderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_rgb, d_disp, d_depth, d_ent, d_raw, d_pts):
         model = ctx.model
-        _refuse_changed_params(model, ctx.params_at, ctx.pack_serial)      # (a replaced STASH is refused by the library itself: generation id)
+        _check_backward(ctx, model)                                # (a replaced STASH is refused by the library itself: generation id)
         dev = model.flat.device
         grad = torch.empty(ctx.n_params, device=dev)
         d_rgb = _f32c(d_rgb) if d_rgb is not None else torch.zeros(ctx.shape, device=dev)
@@ -831,7 +745,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
     are accepted and never read, like the reference; ``N_importance > 0`` / ``network_fine`` - which the
     reference silently ignores (there is no fine pass) - are rejected.
 
-    A model in ``latent_draws = "netchunk"`` mode takes its train latents per netchunk (module docstring): ``chunk`` is then the
+    A model in ``latent_draws = "netchunk"`` mode takes its train latents per netchunk (latents.py): ``chunk`` is then the
     ray cut of the reference's batchify_rays that the draw layout follows (``render`` passes its own; None = one cut).
     """
     _need_gpu(ray_batch, "ray_batch")
@@ -856,37 +770,25 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
         t_vals = t_vals.to(dev, torch.float32).contiguous()
     N, S, K = ray_batch.shape[0], t_vals.shape[0], model.K_samples
     rays = _f32c(ray_batch)
-    eps_rows = None
-    per_chunk = _per_netchunk_latents(eps_alpha, eps_rgb)
-    if per_chunk and not is_train:
-        raise ValueError("per-netchunk latents eps_alpha [C,K,1] / eps_rgb [C,K,3] are train-branch only (the eval branch uses the fixed latents)")
-    if is_train and (model.latent_draws == "netchunk" or per_chunk):
-        # per-netchunk latents as ray rows (explicit [C,K,1] / [C,K,3] mean the same in either mode); implicit draws (netchunk mode) in the
-        # reference's order, cut by cut (draw_train_randomness)
-        if eps_alpha is None and eps_rgb is None:
-            tr, chunks = draw_train_randomness(N, S, K, chunk, model.netchunk, perturb, raw_noise_std)
-            t_rand = tr if t_rand is None else t_rand
-        elif per_chunk:
-            chunks = torch.cat([eps_rgb, eps_alpha], -1).to(torch.float32)
-        else:
-            chunks = None                                   # an explicit [K,1] / [K,3]: one set for the launch, as in "launch" mode
-        if chunks is not None:
-            eps_rows = netchunk_eps_rows(chunks, N, S, model.netchunk, chunk).to(dev)
-    # randomness, in the reference's order: t_rand (RUN:524), eps_alpha (MOD:234), eps_rgb (MOD:246)
+    explicit = LT.pack(eps_alpha, eps_rgb)
+    if is_train:
+        # latents.train_latents: the mode's draws in the reference's order (a t_rand of the CPU generator included, unless there is one)
+        tr, eps, _ = LT.train_latents(model.latent_draws, explicit, N=N, S=S, K=K, netchunk=model.netchunk, chunk=chunk, perturb=perturb,
+                                      raw_noise_std=raw_noise_std, own_t_rand=t_rand is not None or pytest)
+        t_rand, eps = (tr if t_rand is None else t_rand), LT.to_device(eps, dev)
+    else:
+        eps = _latents(model, explicit, False, dev)
     if perturb > 0.:
-        if t_rand is None:
-            t_rand = torch.rand([N, S]).to(dev) if not pytest else torch.tensor(__import__("numpy").random.rand(N, S), dtype=torch.float32).to(dev)
+        if t_rand is None:                                  # RUN:524 (eval branch; pytest: RUN:527-529)
+            t_rand = torch.rand([N, S]) if not pytest else torch.tensor(__import__("numpy").random.rand(N, S), dtype=torch.float32)
         t_rand = _f32c(t_rand.to(dev))
     else:
         t_rand = None
-    eps = _latents(model, eps_alpha, eps_rgb, is_train, dev) if eps_rows is None else eps_rows
     flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_TRAIN if is_train else 0)
     model._sync()
 
     fused = network_query_fn is None or getattr(network_query_fn, "_cfnerf_fused", False)
     if not fused:
-        if eps_rows is not None:                            # the network sees points: one row per point (ray row repeated S times)
-            eps = eps_rows.repeat_interleave(S, 0)
         return _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_rand, eps, is_train, lindisp, white_bkgd)
 
     if is_train and N > 0 and torch.is_grad_enabled() and model.flat.requires_grad:
@@ -924,7 +826,7 @@ def _render_rays_hierarchical(ray_batch, network_fn, N_samples, N_importance, is
     tr = None
     if perturb > 0.:
         tr = _f32c((torch.rand([N, S]) if t_rand is None else t_rand).to(dev))
-    eps = _latents(model, eps_alpha, eps_rgb, is_train, dev)
+    eps = _latents(model, LT.pack(eps_alpha, eps_rgb), is_train, dev)
     if u_fine is None:      # det=(perturb == 0.) in nerf-pytorch
         u_fine = torch.linspace(0., 1., steps=N_importance).expand(N, N_importance) if not perturb > 0. else torch.rand(N, N_importance)
     u = _f32c(u_fine.to(dev))
@@ -956,7 +858,8 @@ def _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_ra
     pts0 = torch.empty(N, S, 3, device=rays.device)
     L.check(L.lib().cfnerf_sample_points(L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), L.F_LINDISP if lindisp else 0, N, S, L.ptr(z_vals),
                                          L.ptr(pts0), L.stream()), "cfnerf_sample_points")            # RUN:510-534
-    model._next_eps = eps                    # NeRF_Flows.forward consumes it: a custom query fn honours the explicit latents too
+    # NeRF_Flows.forward consumes it (a custom query fn honours the launch's latents too); the network sees points: one row per point
+    model._next_eps = eps.repeat_interleave(S, 0) if eps.dim() == 3 else eps
     try:
         raw, loss_entropy = network_query_fn(pts0, viewdirs, network_fn, is_val=False, is_test=not is_train)
     finally:

@@ -116,6 +116,23 @@ static int forward_args(cfnerf_model* m, FwdArgs& a, int flags, int64_t n, int s
     return CFNERF_OK;
 }
 
+// the train branch of cfnerf_render_fwd / cfnerf_network_fwd: STASH implies TRAIN (written to `flags`), TRAIN needs entropy_out, rows are train-only
+static int train_flags(int& flags, const float* entropy_out) {
+    if (flags & CFNERF_F_STASH) flags |= CFNERF_F_TRAIN;
+    if ((flags & CFNERF_F_TRAIN) && !entropy_out) return fail(CFNERF_E_INVALID, "TRAIN needs entropy_out");
+    if ((flags & CFNERF_F_EPS_ROWS) && !(flags & CFNERF_F_TRAIN))
+        return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_ROWS is a train-branch mode (the eval branch uses the fixed [K,4] latents)");
+    return CFNERF_OK;
+}
+
+// ... and the launch that ends it: the entropy over n * s points; with STASH also the backward's copies of a ray launch's `rays` and of a [K,4] set
+static int finish_train_fwd(cfnerf_model* m, int grid, const float* eps, int64_t n, int s, int K, int flags, const float* rays, float* entropy_out, hipStream_t st) {
+    const bool keep = flags & CFNERF_F_STASH, rows = flags & CFNERF_F_EPS_ROWS;
+    HIPCHK(launch_entropy_finalize(m->d_ent_partials, grid, m->flat, eps, K, (double)n * s * K, entropy_out, (keep && !rows) ? m->d_eps : nullptr,
+                                   rays, (keep && rays) ? m->stash.rays : nullptr, rays ? n * 11 : 0, rows ? n : 0, s, st));
+    return CFNERF_OK;
+}
+
 // the fused forward of a ray launch, between the timing events of cfnerf_timing_enable
 static int timed_fused_fwd(cfnerf_model* m, const FwdArgs& a, bool train, hipStream_t st, int* grid) {
     if (m->timing) HIPCHK(hipEventRecord(m->fr0[m->fwd_launches % kFwdRing], st));
@@ -271,9 +288,8 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
     if (!maps && !kstats_opt) return fail(CFNERF_E_INVALID, "either the per-K maps or kstats_opt must be requested");
     if (kstats_opt && K < 2) return fail(CFNERF_E_INVALID, "kstats needs K >= 2 (std * n/(n-1))");
     hipStream_t st = (hipStream_t)s;
-    if (flags & CFNERF_F_STASH) flags |= CFNERF_F_TRAIN;
+    if (int rc = train_flags(flags, entropy_out)) return rc;
     const bool train = flags & CFNERF_F_TRAIN;
-    if (train && !entropy_out) return fail(CFNERF_E_INVALID, "TRAIN needs entropy_out");
     FwdArgs a{};
     a.rays = rays; a.t_vals = t_vals; a.t_rand = z_vals_opt ? nullptr : t_rand; a.z_in = z_vals_opt; a.eps = eps;
     a.N = N; a.S = S; a.P = N * (int64_t)S;
@@ -283,18 +299,12 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
     a.enc_scratch = m->d_enc_scratch;
     const bool keep = flags & CFNERF_F_STASH;
     if (keep && !maps) return fail(CFNERF_E_INVALID, "STASH needs the per-K maps");
-    const bool rows = flags & CFNERF_F_EPS_ROWS;
-    if (rows && !train) return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_ROWS is a train-branch mode (the eval branch uses the fixed [K,4] latents)");
     if (int rc = forward_args(m, a, flags, N, S, K, false)) return rc;
     if (keep) { a.st_z = m->stash.z; a.st_at = m->stash.at; }
-    // (with STASH, q.rays and m->d_eps, the backward's own copies of the step's rays and latents, are written by the copy blocks of the
-    //  entropy_finalize launch below - the forward itself reads the caller's)
+    // (with STASH the backward's own copies of the step's rays and latents are written by finish_train_fwd - the forward reads the caller's)
     int grid = 0;
     if (int rc = timed_fused_fwd(m, a, train, st, &grid)) return rc;
-    if (train)
-        HIPCHK(launch_entropy_finalize(m->d_ent_partials, grid, m->flat, eps, K, (double)a.P * K, entropy_out, (keep && !rows) ? m->d_eps : nullptr,
-                                       rays, keep ? m->stash.rays : nullptr, N * 11, rows ? N : 0, S, st));
-    return CFNERF_OK;
+    return train ? finish_train_fwd(m, grid, eps, N, S, K, flags, rays, entropy_out, st) : CFNERF_OK;
 }
 
 int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, const float* eps, int64_t N, int S, int K, int flags,
@@ -333,24 +343,16 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
     if (P < 0 || P > 0x7fffffff) return fail(CFNERF_E_INVALID, "bad P");
     if (P == 0) return CFNERF_OK;
     if (!x || !eps || !raw) return fail(CFNERF_E_INVALID, "NULL argument");
-    if (flags & CFNERF_F_STASH) flags |= CFNERF_F_TRAIN;
+    if (int rc = train_flags(flags, entropy_out)) return rc;
     const bool train = flags & CFNERF_F_TRAIN;
-    if (train && !entropy_out) return fail(CFNERF_E_INVALID, "TRAIN needs entropy_out");
-    const bool rows = flags & CFNERF_F_EPS_ROWS;
-    if (rows && !train) return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_ROWS is a train-branch mode (the eval branch uses the fixed [K,4] latents)");
     hipStream_t st = (hipStream_t)s;
     FwdArgs a{};
     a.eps = eps; a.x = x; a.P = P; a.N = 0; a.S = 1; a.raw = raw;
     a.ent_partials = train ? m->d_ent_partials : nullptr;
     if (int rc = forward_args(m, a, flags, 1, (int)P, K, true)) return rc;      // points-mode stash: ONE "ray" of P samples
-    if ((flags & CFNERF_F_STASH) && !train)      // (else: entropy_finalize keeps them)
-        HIPCHK(hipMemcpyAsync(m->d_eps, eps, (size_t)K * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
     int grid = 0;
     HIPCHK(launch_fused_fwd(a, m->plan.tab, 1, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, &grid));
-    if (train)
-        HIPCHK(launch_entropy_finalize(m->d_ent_partials, grid, m->flat, eps, K, (double)P * K, entropy_out,
-                                       ((flags & CFNERF_F_STASH) && !rows) ? m->d_eps : nullptr, nullptr, nullptr, 0, rows ? P : 0, 1, st));
-    return CFNERF_OK;
+    return train ? finish_train_fwd(m, grid, eps, P, 1, K, flags, nullptr, entropy_out, st) : CFNERF_OK;
 }
 
 int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K,

@@ -12,12 +12,13 @@ entropy_local, so the SUM over ranks is the gradient of the global means for equ
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
 from . import _lib as L
-from .api import (LATENT_DRAWS, NeRF_Flows, _draw_pairs, _f32c, _pack_rays, _unwrap, draw_train_randomness, netchunk_count,
-                  netchunk_eps_rows, t_vals_table)
+from . import latents as LT
+from .api import NeRF_Flows, _f32c, _pack_rays, _unwrap, t_vals_table
 
 
 def backward_available() -> bool:
@@ -42,17 +43,23 @@ def lr_at(lrate: float, lrate_decay: int, start: int, t: int) -> float:
     return lrate * (0.1 ** ((start + t - 1) / (lrate_decay * 1000)))
 
 
+def _collective_(op, t: torch.Tensor, group=None):
+    """The in-place collective ``op(tensor)`` on ``t``; a gloo group (CPU tests, ranks sharing one GPU) gets a GPU tensor through a host copy."""
+    import torch.distributed as dist
+    if t.is_cuda and dist.get_backend(group) == "gloo":
+        host = t.cpu()
+        op(host)
+        t.copy_(host)
+    else:
+        op(t)
+    return t
+
+
 def allreduce_sum_(grad: torch.Tensor, world: int, group=None, force: bool = False):
-    """ONE sum all-reduce of the flat buffer (RCCL over xGMI when the group's backend is "nccl").  A gloo group (CPU
-    tests, two test processes sharing one GPU) is served through a host staging copy."""
+    """ONE sum all-reduce of the flat buffer (RCCL over xGMI when the group's backend is "nccl")."""
     if world > 1 or force:
         import torch.distributed as dist
-        if grad.is_cuda and dist.get_backend(group) == "gloo":
-            host = grad.cpu()
-            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
-            grad.copy_(host)
-        else:
-            dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=group)
+        _collective_(lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group), grad, group)
     return grad
 
 
@@ -63,21 +70,21 @@ class Trainer:
     """Fused train step on one rank.  Multi-GPU: construct with ``world_size`` (and ``group``) after
     ``torch.distributed.init_process_group``; every rank renders its own shard of the step's rays.
 
-    Latent samples: the reference draws eps once per forward call (MOD:234,246); here every rank must use the SAME eps in
-    a step.  That is enforced, not assumed: rank 0 draws the latents of step t+1 and they travel in a 4*K-float tail of
+    Latent samples (latents.py describes draw order and layout): the reference draws eps once per forward call; here every rank must
+    use the SAME eps in a step.  That is enforced, not assumed: rank 0 draws the latents of step t+1 and they travel in a 4*K-float tail of
     the step-t gradient all-reduce (the other ranks contribute zeros there), so no extra collective and no reliance on
     identical seeding; step 0 uses one broadcast.  An explicit ``eps=`` argument overrides this (tests, benchmarks): ``[K,4]`` for
     the whole step or ``[N,K,4]``, one row per ray of this rank's shard.
 
-    ``latent_draws="netchunk"``: the reference's per-netchunk latents (api.draw_train_randomness).  A step draws the
-    ``C = netchunk_count(N_global, S, netchunk, chunk)`` latent pairs of the GLOBAL batch (on one process together with t_rand, in the
-    reference's order), every rank takes the rows of its own ray range (shard_bounds), and the ``C*K*4`` latents travel in the
-    all-reduce tail like the one set of the default mode.  ``eps_chunks=[C,K,4]`` gives them explicitly."""
+    ``latent_draws="netchunk"``: the reference's per-netchunk latents (latents.py has the draw order and the row layout).  A step
+    draws the ``C = netchunk_count(N_global, S, netchunk, chunk)`` latent pairs of the GLOBAL batch (on one process together with t_rand),
+    every rank takes the rows of its own ray range (shard_bounds), and the ``C*K*4`` latents travel in the all-reduce tail like the one
+    set of the default mode.  ``eps_chunks=[C,K,4]`` gives them explicitly."""
 
     def __init__(self, net, lrate=5e-4, lrate_decay=250, beta1=0.0, world_size=1, group=None, start=0, force_allreduce=False,
                  overlap_comm=False, time_comm=False, max_rays_per_launch=None, latent_draws="launch", netchunk=1024 * 64, chunk=1024 * 32):
-        if latent_draws not in LATENT_DRAWS:
-            raise ValueError(f"latent_draws must be one of {LATENT_DRAWS}, got {latent_draws!r}")
+        if latent_draws not in LT.LATENT_DRAWS:
+            raise ValueError(f"latent_draws must be one of {LT.LATENT_DRAWS}, got {latent_draws!r}")
         self.latent_draws, self.netchunk, self.chunk = latent_draws, int(netchunk), (int(chunk) if chunk else None)
         # max_rays_per_launch: a step's shard larger than this is walked in EQUAL slices (forward -> loss -> backward per slice, the
         # gradient accumulated by cfnerf_render_bwd_accumulate, ONE exchange and ONE Adam step at the end): the train-step workspace
@@ -183,61 +190,31 @@ class Trainer:
             out.update(exposed_ms_mean=sum(ms) / len(ms), exposed_ms_max=max(ms), exposed_ms_min=min(ms), steps=len(ms))
         return out
 
-    def _n_latents(self):
-        """Shape of the latents one step exchanges: [K,4], or the [C,K,4] netchunk pairs of the current global batch."""
-        K = self.net.K_samples
-        return (K, 4) if self.latent_draws == "launch" else (self._n_chunks, K, 4)
+    # ---- the latents that ride in the all-reduce tail: shape (K,4), or the (C,K,4) netchunk pairs of the step's global batch ----------
+    def _draw(self, shape):
+        """Fresh pairs of ``shape`` on the device (pinned, non-blocking: the host keeps running ahead)."""
+        return LT.to_device(LT.draw_pairs(math.prod(shape[:-2]), shape[-2]).reshape(shape), self.net.flat.device)
 
-    def _draw(self):
-        if self.latent_draws == "launch":
-            return self.net.draw_eps()
-        return _draw_pairs(self._n_chunks, self.net.K_samples).pin_memory().to(self.net.flat.device, non_blocking=True)
-
-    def _tail(self, numel):
+    def _tail(self, shape):
         """The latents tail of the all-reduce buffer, grown (with the gradient view) when a netchunk step needs more than 4*MAX_K."""
-        n = self.net.n_params
+        n, numel = self.net.n_params, math.prod(shape)
         if self.gbuf.numel() < n + numel:
             self.gbuf = torch.zeros(n + numel, device=self.gbuf.device)
             self.grad = self.gbuf[:n]
             self._xplan = None
         return self.gbuf[n:n + numel]
 
-    def _step_eps(self):
-        """Latents of the coming step, identical on every rank."""
-        net = self.net
+    def _step_eps(self, shape=None):
+        """Latents of the coming step (default shape: "launch" mode's ``[K,4]``), identical on every rank and on every call before it."""
+        shape = (self.net.K_samples, 4) if shape is None else tuple(shape)
         if self.world == 1 and not self.force_allreduce:
-            return self._draw()
-        if self._eps_next is None or tuple(self._eps_next.shape) != self._n_latents():    # first step: one broadcast from rank 0
+            return self._draw(shape)
+        if self._eps_next is None or tuple(self._eps_next.shape) != shape:             # first step: one broadcast from rank 0
             import torch.distributed as dist
-            eps = self._draw() if self.rank == 0 else torch.zeros(*self._n_latents(), device=net.flat.device)
-            if eps.is_cuda and dist.get_backend(self.group) == "gloo":
-                host = eps.cpu()
-                dist.broadcast(host, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
-                eps = host.to(eps.device)
-            else:
-                dist.broadcast(eps, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
-            return eps
+            eps = self._draw(shape) if self.rank == 0 else torch.zeros(*shape, device=self.net.flat.device)
+            src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+            self._eps_next = _collective_(lambda t: dist.broadcast(t, src=src, group=self.group), eps, self.group)
         return self._eps_next
-
-    def _queue_next_eps(self):
-        """Before the all-reduce: rank 0 writes the NEXT step's latents behind the gradient, everyone else zeros."""
-        shape = self._n_latents()
-        numel = 1
-        for d in shape:
-            numel *= d
-        tail = self._tail(numel)
-        if self.rank == 0:
-            tail.copy_(self._draw().reshape(-1))             # pinned, non-blocking: the host keeps running ahead
-        else:
-            tail.zero_()
-
-    def _take_next_eps(self):
-        shape = self._n_latents()
-        n = self.net.n_params
-        numel = 1
-        for d in shape:
-            numel *= d
-        self._eps_next = self.gbuf[n:n + numel].reshape(shape).clone()
 
     def _buffers(self, N, K):
         if self._buf_n != (N, K):
@@ -258,9 +235,7 @@ class Trainer:
         net, lib, st = self.net, L.lib(), L.stream()
         rows = lambda t: t[a:b] if t is not None else None
         n, K = b - a, net.K_samples
-        if eps.dim() == 3:                  # one latent row per ray (CFNERF_F_EPS_ROWS): the slice's rows
-            if eps.shape[0] != self.packed.shape[0]:
-                raise ValueError(f"latent rows for {eps.shape[0]} rays, the shard has {self.packed.shape[0]}")
+        if LT.check_rows(eps, self.packed.shape[0], "rays of the shard"):         # CFNERF_F_EPS_ROWS: the slice's rows
             eps, flags = eps[a:b], flags | L.F_EPS_ROWS
         L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed[a:b]), L.ptr(t_vals), L.ptr(rows(t_rand)), L.ptr(rows(z_vals)), L.ptr(eps),
                                       n, S, K, flags | (L.F_STASH if grad is not None else 0), L.ptr(self.rgb_map[a:b]), L.ptr(self.disp[a:b]),
@@ -284,33 +259,23 @@ class Trainer:
         S = t_vals.shape[0]
         self._buffers(N, K)
         _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far, out=self.packed)
-        if self.latent_draws == "netchunk" and eps is None:
-            # the GLOBAL batch's per-netchunk pairs, expanded to ray rows; this rank takes its own range (the union of the shards is the
-            # one-process batch).  One process drawing implicitly: t_rand and the pairs in the reference's order
-            Ng = N * self.world
-            if eps_chunks is None:
-                if self.world == 1 and not self.force_allreduce:
-                    tr, eps_chunks = draw_train_randomness(Ng, S, K, self.chunk, self.netchunk, perturb)
-                    t_rand = tr.to(dev) if t_rand is None else t_rand
-                else:
-                    raise RuntimeError("netchunk latents of a sharded step come from Trainer.step (or pass eps_chunks=)")
-            a, b = self.rank * N, (self.rank + 1) * N
-            self.last_eps_chunks = eps_chunks                               # (the step's pairs: identical on every rank)
-            eps = netchunk_eps_rows(_f32c(eps_chunks).to(dev), Ng, S, self.netchunk, self.chunk)[a:b]
-        if perturb > 0. and t_rand is None:
-            t_rand = torch.rand(N, S, device=dev)
-        if perturb <= 0.:
-            t_rand = None
         if eps is None:
-            eps = net.draw_eps()
-        eps = _f32c(eps).to(dev)
-        if eps.dim() == 3 and eps.shape[0] != N:
-            raise ValueError(f"latent rows for {eps.shape[0]} rays, the shard has {N}")
+            if self.latent_draws == "netchunk" and eps_chunks is None and (self.world > 1 or self.force_allreduce):
+                raise RuntimeError("netchunk latents of a sharded step come from Trainer.step (or pass eps_chunks=)")
+            # the GLOBAL batch's latents; of rows this rank takes its own range (the union of the shards is the one-process batch).  As ever:
+            # an implicit netchunk draw brings the CPU generator's t_rand, any other t_rand is drawn on the DEVICE below; no raw_noise_std
+            tr, eps, pairs = LT.train_latents(self.latent_draws, None if eps_chunks is None else _f32c(eps_chunks), N=N * self.world, S=S, K=K,
+                                              netchunk=self.netchunk, chunk=self.chunk, perturb=perturb)
+            t_rand = tr if t_rand is None else t_rand
+            if pairs is not None:
+                self.last_eps_chunks = pairs                                # (the step's pairs: identical on every rank)
+                eps = eps[self.rank * N:(self.rank + 1) * N]
+        t_rand = None if perturb <= 0. else _f32c(torch.rand(N, S, device=dev) if t_rand is None else t_rand).to(dev)
+        eps = LT.to_device(_f32c(eps), dev)
         self._eps_rows = eps if eps.dim() == 3 else None
         net._sync()
         flags = L.F_TRAIN | (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
         n_sl = self.n_slices(N)
-        t_rand = _f32c(t_rand).to(dev) if t_rand is not None else None
         target = _f32c(target)
         # the shard in n_sl equal slices: every loss term is taken with n_total = the FULL batch and beta1 / (world n_sl) on the slice's
         # entropy (equal slices: the mean of the slice means is the batch mean), so the slice gradients and the scalar contributions ADD.
@@ -350,18 +315,20 @@ class Trainer:
     def _step(self, forward_backward, exchange, H, W, focal, rays, target, kw):
         """Body of step / step_hierarchical: the step's latents, forward + backward, the gradient exchange, Adam, re-pack."""
         dist_on = self.world > 1 or self.force_allreduce
+        shape = (self.net.K_samples, 4)             # what the ranks exchange for the next step: one set, or the global batch's pairs
         if self.latent_draws == "netchunk":
             S = (kw.get("t_vals").shape[0] if kw.get("t_vals") is not None else t_vals_table().shape[0])
-            self._n_chunks = netchunk_count(rays[1].reshape(-1, 3).shape[0] * self.world, S, self.netchunk, self.chunk)
-            if dist_on:
-                self._tail(self._n_chunks * self.net.K_samples * 4)       # (grown BEFORE the backward writes the gradient view)
-        if kw.get("eps") is None and kw.get("eps_chunks") is None and dist_on:
-            kw["eps_chunks" if self.latent_draws == "netchunk" else "eps"] = self._step_eps()
+            shape = (LT.netchunk_count(rays[1].reshape(-1, 3).shape[0] * self.world, S, self.netchunk, self.chunk), *shape)
+        if dist_on:
+            tail = self._tail(shape)                                        # (grown BEFORE the backward writes the gradient view)
+            if kw.get("eps") is None and kw.get("eps_chunks") is None:
+                kw["eps_chunks" if len(shape) == 3 else "eps"] = self._step_eps(shape)
         forward_backward(H, W, focal, rays, target, **kw)
         if dist_on:
-            self._queue_next_eps()
+            # rank 0 writes the NEXT step's latents behind the gradient, everyone else zeros; after the sum every rank holds them
+            tail.copy_(self._draw(shape).reshape(-1)) if self.rank == 0 else tail.zero_()
             self._timed_exchange(exchange)
-            self._take_next_eps()
+            self._eps_next = tail.reshape(shape).clone()
         lr = lr_at(self.lrate, self.lrate_decay, self.start, self.t)
         self.t += 1
         net = self.net
