@@ -133,6 +133,20 @@ def get_rays(H, W, focal, c2w):
     return packed[:, 0:3].reshape(H, W, 3), packed[:, 3:6].reshape(H, W, 3)
 
 
+def get_rays_by_coord(H, W, focal, c2w, coords):
+    """Rays through FRACTIONAL pixel coordinates ``coords [n,2] = (x, y)`` of the view ``c2w [3,>=4]`` (HLP:440-445, the key-point rays
+    of depth supervision): ``rays_o, rays_d [n,3]`` fp32 on ``coords``' device.  Plain torch: it runs once per view when a
+    data.DepthRayPool is built, never per step."""
+    coords = torch.as_tensor(coords)
+    dev = coords.device
+    coords = coords.to(torch.float32)
+    c2w = torch.as_tensor(c2w, dtype=torch.float32).to(dev)
+    x, y = (coords[:, 0] - W * .5) / focal, -(coords[:, 1] - H * .5) / focal
+    dirs = torch.stack([x, y, -torch.ones_like(x)], -1)
+    rays_d = torch.sum(dirs[:, None, :] * c2w[:3, :3], -1)
+    return c2w[:3, -1].expand(rays_d.shape), rays_d
+
+
 def ndc_rays(H, W, focal, near, rays_o, rays_d):
     """HLP:360-377 on ``cfnerf_ndc_rays``."""
     _need_gpu(rays_d, "rays_d")

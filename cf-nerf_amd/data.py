@@ -11,12 +11,15 @@ rank holds the whole pool (as the reference holds ``rays_rgb_train`` on its one 
 permutation per epoch for all ranks - and a step consumes a window of ``G * N_rand`` rows of which rank r takes rows
 ``[i + r * N_rand, i + (r + 1) * N_rand)``: the union of the shards is the batch a one-process pool with
 ``N_rand_global = G * N_rand`` delivers, every rank re-shuffles at the same step, and nothing is exchanged per step.
+
+``DepthRayPool`` feeds the key-point rays of depth supervision (the reference's ``rays_depth [M,4,3]``, RUN:887-912, 965-977) through the
+same feeder.
 """
 from __future__ import annotations
 
 import torch
 
-from .api import _pack_rays
+from .api import _pack_rays, get_rays_by_coord
 
 
 class RayPool:
@@ -120,8 +123,11 @@ class RayPool:
             raise RuntimeError(f"RayPool(sync='seed'): the ranks drew DIFFERENT permutations for epoch {self.epoch} from seed {self.seed} "
                                "(different devices or generator algorithms); use sync='broadcast'")
 
+    _TABLE = "rays_rgb"                 # the attribute holding the pool's [M,*,3] table (DepthRayPool shares the feeder on another)
+
     def _permutation(self):
-        M, dev = self.rays_rgb.shape[0], self.rays_rgb.device
+        table = getattr(self, self._TABLE)
+        M, dev = table.shape[0], table.device
         if self.world == 1 and self.seed is None:
             return torch.randperm(M, device=dev, generator=self.generator)
         if self.world == 1 or self.sync == "seed":
@@ -149,10 +155,10 @@ class RayPool:
         return idx
 
     def _shuffle(self):
-        self.rays_rgb = self.rays_rgb[self._permutation()]
+        setattr(self, self._TABLE, getattr(self, self._TABLE)[self._permutation()])
 
     def __len__(self):
-        return self.rays_rgb.shape[0]
+        return getattr(self, self._TABLE).shape[0]
 
     @property
     def global_batch(self):
@@ -162,23 +168,76 @@ class RayPool:
         """RUN:942-951: ``batch_rays [2,N,3]`` (origins, directions) and ``target_s [N,3]`` - this rank's shard of the
         step's window.  The last window of an epoch is short like the reference's last slice; with several ranks it is cut
         to a multiple of ``world`` so that the shards stay equal (the Trainer's gradient normalisation assumes that)."""
-        M, G = self.rays_rgb.shape[0], self.N_rand * self.world
+        batch = self._next_rows()
+        return batch[:2], batch[2]
+
+    def _next_rows(self):
+        """This rank's rows of the step's window, transposed to ``[*,n,3]``; advances the window and re-shuffles an exhausted pool."""
+        table = getattr(self, self._TABLE)
+        M, G = table.shape[0], self.N_rand * self.world
         if M < self.world:
             raise ValueError(f"a pool of {M} rays cannot feed {self.world} ranks")
         if M - self.i_batch < self.world:                     # fewer rays left than ranks: this epoch is over
             self._next_epoch()
+            table = getattr(self, self._TABLE)
         n_win = min(G, M - self.i_batch)
         per = self.N_rand if n_win == G else n_win // self.world
         lo = self.i_batch + self.rank * per
-        batch = self.rays_rgb[lo:lo + per]
+        batch = table[lo:lo + per]
         batch = torch.transpose(batch, 0, 1)
-        batch_rays, target_s = batch[:2], batch[2]
         self.i_batch += G
         if self.i_batch >= M:
             self._next_epoch()                                # "Shuffle data after an epoch!"
-        return batch_rays, target_s
+        return batch
 
     def _next_epoch(self):
         self.epoch += 1
         self._shuffle()
         self.i_batch = 0
+
+
+class DepthRayPool(RayPool):
+    """The feeder of depth supervision's key-point rays (reference: RUN:887-912, 965-977).  ``rays_depth [M,4,3]`` holds per key point
+    of every training view the ray's origin and direction (get_rays_by_coord), its depth x3 and its weight x3.  Rank / world / seed /
+    sync, the window of ``world * N_depth`` rows per step and the re-shuffle of an exhausted pool are RayPool's (its feeder code runs
+    here on this table).  The pool lives where ``depth_gts`` / the table lives - a few thousand rows; Trainer moves a batch to its device."""
+    _TABLE = "rays_depth"
+
+    def __init__(self, depth_gts, poses, H, W, focal, i_train, N_depth=128, generator=None, shuffle=True, rank=0, world=1, seed=None,
+                 group=None, sync="auto", device=None):
+        """``depth_gts``: one dict per view (indexed like ``poses``) with ``coord [n,2]`` (x, y in pixels), ``depth [n]``, ``weight [n]`` -
+        what the reference's load_colmap_depth returns; ``N_depth`` rays PER RANK and step."""
+        self.H, self.W, self.focal = int(H), int(W), float(focal)
+        self._init_feeder(N_depth, generator, rank, world, seed, group, sync)
+        poses = torch.as_tensor(poses, dtype=torch.float32)
+        f32 = lambda a: torch.as_tensor(a, dtype=torch.float32, device=device)
+        rows = []
+        for v in i_train:
+            d = depth_gts[int(v)]
+            ro, rd = get_rays_by_coord(self.H, self.W, self.focal, poses[int(v), :3, :4], f32(d["coord"]))
+            x3 = lambda a: f32(a)[:, None].expand(-1, 3)
+            rows.append(torch.stack([ro, rd, x3(d["depth"]), x3(d["weight"])], 1))                     # [n, ro+rd+depth+weight, 3]
+        self.rays_depth = torch.cat(rows, 0)                                                           # [M, 4, 3]
+        if shuffle:
+            self._shuffle()
+
+    @classmethod
+    def from_rays_depth(cls, rays_depth, N_depth=128, generator=None, shuffle=True, rank=0, world=1, seed=None, group=None, sync="auto"):
+        """The feeder over a ready ``rays_depth [M,4,3]`` table (RUN:900) - any device."""
+        self = cls.__new__(cls)
+        self.H = self.W = self.focal = None
+        self._init_feeder(N_depth, generator, rank, world, seed, group, sync)
+        self.rays_depth = rays_depth
+        if shuffle:
+            self._shuffle()
+        return self
+
+    @property
+    def N_depth(self):
+        return self.N_rand
+
+    def next_batch(self):
+        """RUN:965-977: ``batch_rays_depth [2,n,3]``, ``target_depth [n]`` and ``ray_weights [n]`` (loaded and never used by the
+        reference's loss, RUN:970) - this rank's shard of the step's window."""
+        batch = self._next_rows()
+        return batch[:2], batch[2, :, 0], batch[3, :, 0]

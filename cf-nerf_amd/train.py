@@ -8,6 +8,12 @@ world_size > 1 -> fused Adam on the flat buffers -> re-pack.  Rays are sharded b
 Gradient normalisation across ranks: the reference's losses are means over rays / points
 (RUN:1042,1045).  Each rank computes the gradient of  nll_local_sum / (3 * N_total) + (beta1 / world) *
 entropy_local, so the SUM over ranks is the gradient of the global means for equal shards.
+
+Depth supervision (the reference's ``colmap_depth``, RUN:1009-1024,1052-1054): a step may carry N_d extra rays through key
+points of known depth; they are rendered in the SAME launch behind the N colour rays and add
+``depth_lambda * mean_i (mean_K depth_map[N + i] - target_depth[i])^2`` to the loss.  The rule above extends by one term: each
+rank differentiates  nll_local / (3 N world) + depth_lambda * sq_local / (N_d world) + (beta1 / world) * entropy_local.
+``depth_term`` forms that term and its cotangent ``d_depth_map`` on the device from the forward's depth map.
 """
 from __future__ import annotations
 
@@ -66,6 +72,19 @@ def allreduce_sum_(grad: torch.Tensor, world: int, group=None, force: bool = Fal
 MAX_K = 128     # kMaxK of the kernels
 
 
+def depth_term(depth_rows: torch.Tensor, target_depth: torch.Tensor, depth_lambda: float, n_depth_total: int):
+    """The depth-supervision term of ``n`` key-point rays (RUN:1020,1023,1053-1054) and its cotangent:
+    ``contribution [1] = depth_lambda * sum_i (mean_k depth_rows[i,:] - target_depth[i])^2 / n_depth_total`` and
+    ``d_depth_rows [n,K] = d contribution / d depth_rows = 2 depth_lambda (mean_k depth_rows[i,:] - target_depth[i]) / (n_depth_total K)``.
+    ``n_depth_total`` is the step's number of depth rays over all ranks and slices, so contributions add up to
+    ``depth_lambda * img2mse`` and cotangents concatenate.  Tensors in and out on the inputs' device, no host synchronisation.
+    (The one place the term is formed: ``cfnerf_loss_fwd_bwd`` has no argument that could carry it.)"""
+    K = depth_rows.shape[-1]
+    diff = depth_rows.mean(-1) - target_depth
+    d_rows = (diff * (2.0 * depth_lambda / (n_depth_total * K)))[:, None].expand(-1, K).contiguous()
+    return d_rows, ((diff * diff).sum() * (depth_lambda / n_depth_total)).reshape(1)
+
+
 class Trainer:
     """Fused train step on one rank.  Multi-GPU: construct with ``world_size`` (and ``group``) after
     ``torch.distributed.init_process_group``; every rank renders its own shard of the step's rays.
@@ -79,10 +98,15 @@ class Trainer:
     ``latent_draws="netchunk"``: the reference's per-netchunk latents (latents.py has the draw order and the row layout).  A step
     draws the ``C = netchunk_count(N_global, S, netchunk, chunk)`` latent pairs of the GLOBAL batch (on one process together with t_rand),
     every rank takes the rows of its own ray range (shard_bounds), and the ``C*K*4`` latents travel in the all-reduce tail like the one
-    set of the default mode.  ``eps_chunks=[C,K,4]`` gives them explicitly."""
+    set of the default mode.  ``eps_chunks=[C,K,4]`` gives them explicitly.
+
+    ``depth_lambda > 0``: ``step`` / ``forward_backward`` accept ``depth_rays=`` / ``target_depth=`` (data.DepthRayPool feeds them) and
+    add the reference's depth-supervision term (module docstring; forward_backward has the entropy rule).  Without depth rays a step is
+    the plain step whatever ``depth_lambda`` is."""
 
     def __init__(self, net, lrate=5e-4, lrate_decay=250, beta1=0.0, world_size=1, group=None, start=0, force_allreduce=False,
-                 overlap_comm=False, time_comm=False, max_rays_per_launch=None, latent_draws="launch", netchunk=1024 * 64, chunk=1024 * 32):
+                 overlap_comm=False, time_comm=False, max_rays_per_launch=None, latent_draws="launch", netchunk=1024 * 64, chunk=1024 * 32,
+                 depth_lambda=0.0):
         if latent_draws not in LT.LATENT_DRAWS:
             raise ValueError(f"latent_draws must be one of {LT.LATENT_DRAWS}, got {latent_draws!r}")
         self.latent_draws, self.netchunk, self.chunk = latent_draws, int(netchunk), (int(chunk) if chunk else None)
@@ -114,6 +138,10 @@ class Trainer:
         # beta1 / world on the shard's entropy): their sum over ranks is the global value (RUN:1042-1050)
         self.scalars = torch.zeros(4, device=dev)
         self.entropy = torch.zeros(1, device=dev)
+        # depth supervision: weight of the term, and this rank's contribution to the step's depth_loss (the reference's train/depth_loss)
+        self.depth_lambda = float(depth_lambda)
+        self.depth_loss = torch.zeros(1, device=dev)
+        self._d_depth_n = None
         self.t = 0
         self._buf_n = None
         self._eps_rows = None           # this step's latent rows (netchunk mode): the stash reads them until the backward
@@ -225,13 +253,51 @@ class Trainer:
             self.depth = torch.empty(N, K, device=dev)
             self.d_rgb = torch.empty(N, 3, K, device=dev)
             self._buf_n = (N, K)
+            self._d_depth_n = None
+
+    def _depth_buffers(self, n_colour, N, K):
+        """The cotangent buffers of a depth-supervised launch of ``n_colour`` colour rows then ``N - n_colour`` depth rows: ``d_rgb`` of the
+        depth rows and ``d_depth`` of the colour rows are zero and stay zero (the loss writes colour rows of ``d_rgb`` only, depth_term depth
+        rows of ``d_depth`` only), so they are cleared when the buffers or the split change, not per step."""
+        if self._d_depth_n != (n_colour, N, K):
+            self.d_rgb[n_colour:].zero_()
+            self.d_depth = torch.zeros(N, K, device=self.d_rgb.device)
+            self._d_depth_n = (n_colour, N, K)
+
+    def _check_depth(self, depth_rays, target_depth, n_colour, S):
+        """Refusals of a depth-supervised step; returns None (no depth rays) or ``(depth_rays, target_depth [N_d], first)`` where ``first``
+        is None or, in netchunk mode when the batch is several network calls, the rays of the first one."""
+        if depth_rays is None and target_depth is None:
+            return None
+        if depth_rays is None or target_depth is None:
+            raise ValueError("depth_rays and target_depth go together")
+        if self.depth_lambda == 0.0:
+            raise ValueError("depth rays given to a Trainer with depth_lambda = 0: the depth term would be dropped")
+        n_d = depth_rays[1].reshape(-1, 3).shape[0]
+        target_depth = target_depth.reshape(-1)
+        if target_depth.shape[0] != n_d or n_d == 0:
+            raise ValueError(f"{n_d} depth rays, {target_depth.shape[0]} depth targets")
+        first = None
+        if self.latent_draws == "netchunk":
+            N = n_colour + n_d
+            if self.world > 1:
+                raise NotImplementedError("latent_draws='netchunk' with depth rays on several ranks: the reference's ray order puts all colour "
+                                          "rays before all depth rays, the ranks' shards interleave them")
+            if LT.netchunk_count(N, S, self.netchunk, self.chunk) > 1:
+                # the reference cuts the per-POINT entropy tensor to its first n_colour rows (RUN:1024): points of the first network call
+                if self.n_slices(N) > 1:
+                    raise NotImplementedError("latent_draws='netchunk' with depth rays and max_rays_per_launch on a batch of several network "
+                                              "calls: the entropy term is the first network call's alone")
+                first = min(self.netchunk // S, LT.ray_cuts(N, self.chunk)[0][1])
+        return depth_rays, target_depth, first
 
     def _pass(self, a, b, t_vals, t_rand, eps, S, flags, target, beta, scalars, entropy, d_ent, grad=None, accumulate=False, z_vals=None,
-              weights=None):
+              weights=None, depth=None):
         """One pass over rows [a, b) of the packed rays into the persistent buffers: the fused forward (``t_rand`` / ``z_vals`` and the
         optional ``weights [N,S,K]`` output are per-ray too and sliced alike) and, given a ``grad`` buffer, a STASH forward followed by the
         KDE-NLL loss (+ ``beta`` * entropy; means over the step's whole shard) into ``scalars`` and the backward into ``grad``
-        (``accumulate``: added to what it holds)."""
+        (``accumulate``: added to what it holds).  ``depth = (n_colour, target_depth)``: rows from ``n_colour`` on are depth rays - the
+        loss runs on the pass's colour rows, depth_term on its depth rows, and the backward gets ``d_depth_map``."""
         net, lib, st = self.net, L.lib(), L.stream()
         rows = lambda t: t[a:b] if t is not None else None
         n, K = b - a, net.K_samples
@@ -242,22 +308,60 @@ class Trainer:
                                       L.ptr(self.depth[a:b]), None, L.ptr(rows(weights)), None, None, L.ptr(entropy), st), "cfnerf_render_fwd")
         if grad is None:
             return
-        L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map[a:b]), L.ptr(target[a:b]), L.ptr(entropy), n, K, C.c_float(beta),
-                                        self.packed.shape[0] * self.world, L.ptr(self.d_rgb[a:b]), L.ptr(scalars), st), "cfnerf_loss_fwd_bwd")
+        d_depth = None
+        if depth is None:
+            self._d_depth_n = None                                               # (a plain pass writes every row of d_rgb it covers)
+            L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map[a:b]), L.ptr(target[a:b]), L.ptr(entropy), n, K, C.c_float(beta),
+                                            self.packed.shape[0] * self.world, L.ptr(self.d_rgb[a:b]), L.ptr(scalars), st), "cfnerf_loss_fwd_bwd")
+        else:
+            n_colour, target_depth = depth
+            hi, lo = max(a, min(b, n_colour)), max(a, n_colour)                  # colour rows [a, hi), depth rows [lo, b) of this pass
+            if hi > a:
+                L.check(lib.cfnerf_loss_fwd_bwd(L.ptr(self.rgb_map[a:hi]), L.ptr(target[a:hi]), L.ptr(entropy), hi - a, K, C.c_float(beta),
+                                                n_colour * self.world, L.ptr(self.d_rgb[a:hi]), L.ptr(scalars), st), "cfnerf_loss_fwd_bwd")
+            else:                                                                # no colour row: the entropy term is all the loss kernel would add
+                scalars.zero_()
+                if beta:
+                    scalars[0:1] = beta * entropy
+            if b > lo:
+                n_d = self.packed.shape[0] - n_colour
+                self.d_depth[lo:b], part = depth_term(self.depth[lo:b], target_depth[lo - n_colour:b - n_colour], self.depth_lambda,
+                                                      n_d * self.world)
+                scalars[0:1] += part
+                self.depth_loss += part / self.depth_lambda
+                d_depth = self.d_depth[a:b]
         gen = lib.cfnerf_model_stash_generation(net.handle)
         bwd = lib.cfnerf_render_bwd_accumulate if accumulate else lib.cfnerf_render_bwd
-        L.check(bwd(net.handle, gen, L.ptr(self.d_rgb[a:b]), None, L.ptr(d_ent) if self.beta1 else None, L.ptr(grad), st),
-                "cfnerf_render_bwd_accumulate" if accumulate else "cfnerf_render_bwd")
+        L.check(bwd(net.handle, gen, L.ptr(self.d_rgb[a:b]), L.ptr(d_depth), L.ptr(d_ent) if self.beta1 and d_ent is not None else None,
+                    L.ptr(grad), st), "cfnerf_render_bwd_accumulate" if accumulate else "cfnerf_render_bwd")
 
     def forward_backward(self, H, W, focal, rays, target, t_rand=None, eps=None, near=0., far=1., ndc=True,
-                         lindisp=False, white_bkgd=False, perturb=1., t_vals=None, eps_chunks=None, **_ignored):
-        """Forward + loss + backward of this rank's shard.  Leaves the (un-reduced) gradient in ``self.grad``."""
+                         lindisp=False, white_bkgd=False, perturb=1., t_vals=None, eps_chunks=None, depth_rays=None, target_depth=None,
+                         **_ignored):
+        """Forward + loss + backward of this rank's shard.  Leaves the (un-reduced) gradient in ``self.grad``.
+
+        ``depth_rays [2,N_d,3]`` / ``target_depth [N_d]`` (this rank's shard of the step's key-point rays, ``depth_lambda > 0``): the launch
+        is the colour rays followed by the depth rays - ``t_rand`` / ``eps`` rows cover all ``N + N_d`` rays, the output buffers too -,
+        the KDE-NLL runs on the colour rows, the depth term on the depth rows; ``self.depth_loss`` holds the rank's contribution to the
+        step's ``depth_loss`` and ``self.scalars[0]`` includes ``depth_lambda`` times it.  The entropy term is the launch's (all rays);
+        in netchunk mode on a batch of several network calls it is the FIRST call's alone, as in the reference (RUN:1024 cuts the
+        per-point entropy tensor to its first N rows): that call is one launch, the rest a second one without an entropy cotangent."""
         net = self.net
         dev = net.flat.device
-        N, K = rays[1].reshape(-1, 3).shape[0], net.K_samples
         t_vals = t_vals_table(dev) if t_vals is None else t_vals            # (cached per device)
         S = t_vals.shape[0]
+        N, K = rays[1].reshape(-1, 3).shape[0], net.K_samples
+        depth = self._check_depth(depth_rays, target_depth, N, S)
+        first = None
+        if depth is not None:
+            depth_rays, target_depth, first = depth
+            rays = tuple(torch.cat([_f32c(rays[i].reshape(-1, 3)), _f32c(depth_rays[i].reshape(-1, 3)).to(rays[i].device)], 0) for i in (0, 1))
+            depth = (N, _f32c(target_depth).to(dev))                        # (colour rows, targets of the depth rows behind them)
+            N += target_depth.shape[0]
+            self.depth_loss.zero_()
         self._buffers(N, K)
+        if depth is not None:
+            self._depth_buffers(depth[0], N, K)
         _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far, out=self.packed)
         if eps is None:
             if self.latent_draws == "netchunk" and eps_chunks is None and (self.world > 1 or self.force_allreduce):
@@ -280,6 +384,8 @@ class Trainer:
         # the shard in n_sl equal slices: every loss term is taken with n_total = the FULL batch and beta1 / (world n_sl) on the slice's
         # entropy (equal slices: the mean of the slice means is the batch mean), so the slice gradients and the scalar contributions ADD.
         # One slice writes its scalars and entropy straight into the step's own buffers.
+        if first is not None:
+            return self._first_call_and_rest(first, N, t_vals, t_rand, eps, S, flags, target, depth)
         Ns = N // n_sl
         net.ensure_workspace(Ns, S, K)
         if n_sl == 1:
@@ -293,7 +399,7 @@ class Trainer:
             sc_sum, ent_sum = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         for i in range(n_sl):
             self._pass(i * Ns, (i + 1) * Ns, t_vals, t_rand, eps, S, flags, target, self.beta1 / (self.world * n_sl), sc, ent, d_ent,
-                       grad=self.grad, accumulate=i > 0)
+                       grad=self.grad, accumulate=i > 0, depth=depth)
             if n_sl > 1:
                 sc_sum += sc
                 ent_sum += ent
@@ -301,6 +407,21 @@ class Trainer:
             self.scalars[:3] = sc_sum[:3]
             self.scalars[3] = -10.0 * torch.log10(sc_sum[2])                # HLP:16 on the batch's mse
             self.entropy.copy_(ent_sum / n_sl)
+        return self.grad
+
+    def _first_call_and_rest(self, first, N, t_vals, t_rand, eps, S, flags, target, depth):
+        """Depth-supervised netchunk step on a batch of several network calls (one process): rows [0, first) - the first network call -
+        with the entropy term ``beta1`` * (that call's entropy), rows [first, N) without one; the second launch's gradient is added
+        to the first's and the colour rows' scalar contributions add like slices'."""
+        dev = self.net.flat.device
+        self.net.ensure_workspace(max(first, N - first), S, self.net.K_samples)
+        sc, ent = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
+        self._pass(0, first, t_vals, t_rand, eps, S, flags, target, self.beta1, self.scalars, self.entropy, self.d_ent, grad=self.grad,
+                   depth=depth)
+        self._pass(first, N, t_vals, t_rand, eps, S, flags, target, 0.0, sc, ent, None, grad=self.grad, accumulate=True, depth=depth)
+        sc[:3] += self.scalars[:3]
+        self.scalars[:3] = sc[:3]
+        self.scalars[3] = -10.0 * torch.log10(sc[2])                        # HLP:16 on the batch's mse
         return self.grad
 
     def n_slices(self, N):
@@ -318,7 +439,8 @@ class Trainer:
         shape = (self.net.K_samples, 4)             # what the ranks exchange for the next step: one set, or the global batch's pairs
         if self.latent_draws == "netchunk":
             S = (kw.get("t_vals").shape[0] if kw.get("t_vals") is not None else t_vals_table().shape[0])
-            shape = (LT.netchunk_count(rays[1].reshape(-1, 3).shape[0] * self.world, S, self.netchunk, self.chunk), *shape)
+            n_depth = 0 if kw.get("depth_rays") is None else kw["depth_rays"][1].reshape(-1, 3).shape[0]
+            shape = (LT.netchunk_count((rays[1].reshape(-1, 3).shape[0] + n_depth) * self.world, S, self.netchunk, self.chunk), *shape)
         if dist_on:
             tail = self._tail(shape)                                        # (grown BEFORE the backward writes the gradient view)
             if kw.get("eps") is None and kw.get("eps_chunks") is None:
@@ -340,15 +462,16 @@ class Trainer:
         return self.scalars
 
     def step(self, H, W, focal, rays, target, **kw):
-        """One full train step.  Returns the device tensor [loss, loss_nll, mse, psnr] of the local shard."""
+        """One full train step.  Returns the device tensor [loss, loss_nll, mse, psnr] of the local shard (``depth_rays=`` /
+        ``target_depth=``: the depth-supervised step, see forward_backward)."""
         kw = {k: v for k, v in kw.items() if k in ("t_rand", "eps", "eps_chunks", "near", "far", "ndc", "lindisp", "white_bkgd", "perturb",
-                                                     "t_vals")}
+                                                     "t_vals", "depth_rays", "target_depth")}
         return self._step(self.forward_backward, self._exchange, H, W, focal, rays, target, kw)
 
     # ---- EXTENSION (not in the reference, SURVEY R1 / 8f-4): coarse + fine sampling through the single network -----
     def forward_backward_hierarchical(self, H, W, focal, rays, target, N_samples=64, N_importance=128, coarse_loss=True, t_rand=None,
                                       u_fine=None, eps=None, near=0., far=1., ndc=True, lindisp=False, white_bkgd=False, perturb=1.,
-                                      **_ignored):
+                                      depth_rays=None, target_depth=None, **_ignored):
         """Coarse pass on ``linspace(0,1,N_samples)`` -> ``cfnerf_sample_pdf`` (depths are constants, as nerf-pytorch
         detaches ``z_samples``) -> fine pass on the merged N_samples + N_importance depths, loss and backward.  With
         ``coarse_loss`` the coarse pass keeps a stash and its own loss term is differentiated too
@@ -356,6 +479,8 @@ class Trainer:
         loss_fine + loss_coarse.  Returns it; ``self.scalars`` holds the fine pass's [loss, nll, mse, psnr]."""
         if self.latent_draws == "netchunk":
             raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
+        if depth_rays is not None or target_depth is not None:
+            raise NotImplementedError("depth rays are not supported by the hierarchical-sampling extension")
         net = self.net
         dev = net.flat.device
         N, K, S, Ni = rays[1].reshape(-1, 3).shape[0], net.K_samples, int(N_samples), int(N_importance)
