@@ -698,7 +698,7 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
 def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True, raw=False, weights=False, pts=False, kstats=False,
                 entropy=True):
     """cfnerf_render_fwd of the packed ``rays [N,11]`` into newly allocated outputs.  Returns a dict with ``rgb_map [N,3,K]``,
-    ``disp_map`` / ``depth_map [N,K]`` (``maps``), ``raw [N,S,K,4]``, ``weights [N,S,K]``, ``pts [N,S,3]``, ``kstats [N,8]`` and the
+    ``disp_map`` / ``depth_map [N,K]`` (``maps``), ``raw [N,S,K,4]``, ``weights [N,S,K]``, ``pts [N,S,3]``, ``kstats [N,8]`` ([N,12] with ``L.F_KSTATS_EXT`` in ``flags``) and the
     zeroed accumulator ``entropy [1]``; an output that was not asked for is None.  S is that of ``z_vals [N,S]`` (explicit depths,
     which the library then prefers to ``t_rand``) or of the sample table ``t_vals``."""
     N, K = rays.shape[0], eps.shape[-2]
@@ -708,7 +708,7 @@ def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True,
     dev = rays.device
     new = lambda want, *shape: torch.empty(*shape, device=dev) if want else None
     o = {'rgb_map': new(maps, N, 3, K), 'disp_map': new(maps, N, K), 'depth_map': new(maps, N, K), 'raw': new(raw, N, S, K, 4),
-         'weights': new(weights, N, S, K), 'pts': new(pts, N, S, 3), 'kstats': new(kstats, N, 8),
+         'weights': new(weights, N, S, K), 'pts': new(pts, N, S, 3), 'kstats': new(kstats, N, 12 if flags & L.F_KSTATS_EXT else 8),
          'entropy': torch.zeros(1, device=dev) if entropy else None}
     L.check(L.lib().cfnerf_render_fwd(model.handle, L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), L.ptr(z_vals), L.ptr(eps), N, S, K, flags,
                                       *(L.ptr(t) for t in o.values()), L.stream()), "cfnerf_render_fwd")

@@ -151,6 +151,13 @@ static int check_device(const cfnerf_model* m) {
     return CFNERF_OK;
 }
 
+// CFNERF_F_KSTATS_EXT widens the kstats / sqerr rows of the two render entry points; anywhere else it would be silently ignored
+static int refuse_kstats_ext(int flags, const char* who) {
+    if (flags & CFNERF_F_KSTATS_EXT)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_KSTATS_EXT (it widens kstats / sqerr of cfnerf_render_eval and cfnerf_render_fwd)", who);
+    return CFNERF_OK;
+}
+
 extern "C" int cfnerf_model_destroy(cfnerf_model* m);
 
 extern "C" {
@@ -261,6 +268,7 @@ int cfnerf_embed(const float* x, int64_t P, int multires, float* out, cfnerf_str
 
 int cfnerf_sample_points(const float* rays, const float* t_vals, const float* t_rand, int flags, int64_t N, int S, float* z_vals,
                          float* pts, cfnerf_stream s) {
+    if (int rc = refuse_kstats_ext(flags, "cfnerf_sample_points")) return rc;
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
     if (N == 0) return CFNERF_OK;
     if (!rays || !t_vals || !z_vals) return fail(CFNERF_E_INVALID, "NULL argument");
@@ -289,6 +297,11 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
     if (kstats_opt && K < 2) return fail(CFNERF_E_INVALID, "kstats needs K >= 2 (std * n/(n-1))");
     hipStream_t st = (hipStream_t)s;
     if (int rc = train_flags(flags, entropy_out)) return rc;
+    if (flags & CFNERF_F_KSTATS_EXT) {
+        if (!kstats_opt) return fail(CFNERF_E_INVALID, "CFNERF_F_KSTATS_EXT needs kstats_opt (it widens its rows to 12 floats)");
+        if (flags & (CFNERF_F_STASH | CFNERF_F_EPS_ROWS))
+            return fail(CFNERF_E_UNSUPPORTED, "CFNERF_F_KSTATS_EXT is not built for CFNERF_F_STASH / CFNERF_F_EPS_ROWS launches (evaluation metrics: render without a stash, one latent set)");
+    }
     const bool train = flags & CFNERF_F_TRAIN;
     FwdArgs a{};
     a.rays = rays; a.t_vals = t_vals; a.t_rand = z_vals_opt ? nullptr : t_rand; a.z_in = z_vals_opt; a.eps = eps;
@@ -329,6 +342,7 @@ int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, 
 
 int cfnerf_sample_pdf(const float* rays, const float* t_vals, const float* t_rand, int flags, const float* weights, const float* u,
                       int64_t N, int S, int K, int N_importance, float* z_out, cfnerf_stream s) {
+    if (int rc = refuse_kstats_ext(flags, "cfnerf_sample_pdf")) return rc;
     if (N < 0 || S < 3 || K < 1 || N_importance < 1) return fail(CFNERF_E_INVALID, "bad N/S/K/N_importance (S >= 3)");
     if (S + N_importance > 1024) return fail(CFNERF_E_UNSUPPORTED, "S + N_importance must be <= 1024");
     if (N == 0) return CFNERF_OK;
@@ -340,6 +354,7 @@ int cfnerf_sample_pdf(const float* rays, const float* t_vals, const float* t_ran
 int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_t P, int K, int flags, float* raw,
                        float* entropy_out, cfnerf_stream s) {
     if (int rc = check_common(m, K)) return rc;
+    if (int rc = refuse_kstats_ext(flags, "cfnerf_network_fwd")) return rc;
     if (P < 0 || P > 0x7fffffff) return fail(CFNERF_E_INVALID, "bad P");
     if (P == 0) return CFNERF_OK;
     if (!x || !eps || !raw) return fail(CFNERF_E_INVALID, "NULL argument");

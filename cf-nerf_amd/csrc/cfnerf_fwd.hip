@@ -84,6 +84,58 @@ __device__ __forceinline__ void encode_tile(float* act, const float* rowinfo, co
 }
 
 
+// CFNERF_F_KSTATS_EXT: columns 8..11 of a ray's kstats row and 3..5 of its sqerr row, from the ray's final comp[k] = (r g b depth acc T disp _)
+// in LDS.  One WAVE per quantity with lane = latent (two per lane from 65 latents on) and the composite's wave sums - at K up to 128 a
+// serial walk over k on a few threads is the wrong shape: wave 0 disparity, 1 depth, 2 accumulated opacity, 3 the three colour
+// channels of the NLL.  Two passes (mean, then the centred squares), like the serial columns 3..5.
+//   spread (8, 9, 11): sqrt(sum (x - mean)^2 / K) * K / (K - 1) - np.std * n/(n-1), RUN:1130, the estimator of columns 3..5;
+//   nll_c (sqerr 3..5): the integrand of RUN:1034-1042 - h = torch.std (UNBIASED) * n/(n-1) * (0.8/n)^(-1/7) + 1e-5,
+//                       -log(mean_k[exp(-(rgb_k - gt)^2 / (2 h^2))] (2 pi)^(-1.5) / h + 1e-5) - the TRAIN estimator, not that of columns 3..5,
+//                       operation for operation what loss_kernel (cfnerf_bwd.hip) evaluates: libm expf / logf / powf whatever the
+//                       model's flow-math mode (O(K) per ray and channel: nothing to gain from the hardware transcendentals).
+// Called by every wave of the workgroup after the barrier that makes comp[] final; `wave` is uniform, so the wave sums run with all lanes on.
+// `lane` comes in opaque (lane_id_opaque): the LDS addresses derived from it are formed here, not hoisted in front of the ray loop.
+__device__ __forceinline__ void kstats_ext_epilogue(const float* comp, int K, int wave, int lane, float* __restrict__ ks, const float* __restrict__ gt,
+                                                    float* __restrict__ sq) {
+    if (wave >= 4 || (wave == 3 && gt == nullptr)) return;
+    const float fK = (float)K;
+    const bool l0 = lane < K, l1 = lane + 64 < K;
+    const float* const c0 = comp + lane * 8;
+    const float* const c1 = comp + (lane + 64) * 8;
+    // mean over K and the sum of the centred squares of slot `c`; x0 / x1 keep this lane's (up to) two values
+    auto moments = [&](int c, float& x0, float& x1, float& mean, float& ss) {
+        x0 = l0 ? c0[c] : 0.f; x1 = l1 ? c1[c] : 0.f;
+        mean = comp_sum(x0 + x1) / fK;
+        const float d0 = l0 ? x0 - mean : 0.f, d1 = l1 ? x1 - mean : 0.f;
+        ss = comp_sum(d0 * d0 + d1 * d1);
+    };
+    float x0, x1, mean, ss;
+    if (wave < 3) {
+        moments(wave == 0 ? 6 : (wave == 1 ? 3 : 4), x0, x1, mean, ss);
+        const float unc = sqrtf(ss / fK) * fK / (float)(K - 1);
+        if (lane == 0) {
+            if (wave == 2) { ks[10] = mean; ks[11] = unc; }
+            else ks[8 + wave] = unc;
+        }
+        return;
+    }
+    const float bw = powf(0.8f / fK, -1.f / 7.f);                        // RUN:1036
+    const float c2pi = powf(2.f * 3.14159265358979323846f, -1.5f);      // RUN:1039
+    for (int c = 0; c < 3; ++c) {
+        moments(c, x0, x1, mean, ss);
+        const float sd = sqrtf(ss / (float)(K - 1));                     // torch.std (unbiased)
+        const float H = (sd * fK / (float)(K - 1)) * bw + 1e-05f;        // RUN:1034,1036
+        const float c2 = c2pi / H;
+        const float inv2h2 = 1.f / (2.f * H * H);
+        const float t = gt[c];
+        const float e0 = x0 - t, e1 = x1 - t;
+        const float r0 = l0 ? expf(-(e0 * e0) * inv2h2) * c2 : 0.f;      // RUN:1038-1040
+        const float r1 = l1 ? expf(-(e1 * e1) * inv2h2) * c2 : 0.f;
+        const float m = comp_sum(r0 + r1) * (1.f / fK) + 1e-05f;         // RUN:1041
+        if (lane == 0) sq[3 + c] = -logf(m);                             // RUN:1042
+    }
+}
+
 // the kernarg segment of fused_fwd_kernel as one struct (second argument at the first argument's size rounded up to its own alignment)
 struct FwdKargs { FwdArgs A; NetTab T; };
 static_assert(offsetof(FwdKargs, T) == (sizeof(FwdArgs) + alignof(NetTab) - 1) / alignof(NetTab) * alignof(NetTab), "kernarg layout");
@@ -93,11 +145,15 @@ static_assert(offsetof(FwdKargs, T) == (sizeof(FwdArgs) + alignof(NetTab) - 1) /
 // rows out of LDS.
 // ROWS (train only, CFNERF_F_EPS_ROWS): the latents are one [K,4] row per ray (MODE 0) / per point (MODE 1) instead of one set per
 // launch.  A variant of its own, so the register allocation of the one-set kernels is exactly what it was without the mode.
-template <int W, int MODE /*0 rays, 1 points*/, bool TRAIN, int PREC, bool Q4 = false, bool ROWS = false>
+// EXT (ray mode, CFNERF_F_KSTATS_EXT): kstats rows are [12] and sqerr rows [6] - the ray-output epilogue adds the spread of disparity,
+// depth and accumulated opacity over K and the per-channel KDE negative log-likelihood (kstats_ext_epilogue).  A variant of its own for
+// the same reason as ROWS; it exists for the launches without a stash and without latent rows only.
+template <int W, int MODE /*0 rays, 1 points*/, bool TRAIN, int PREC, bool Q4 = false, bool ROWS = false, bool EXT = false>
 __global__ __launch_bounds__(FwdCfg<W>::NTHR, 2)
 void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
     static_assert(!Q4 || (TRAIN && PREC == PREC_F32), "the Q4 stash layout exists for the fp32 train variants only");
     static_assert(!ROWS || TRAIN, "latent rows are a train-branch mode");
+    static_assert(!EXT || (MODE == 0 && !Q4 && !ROWS), "the extended K-statistics belong to ray launches without a stash and without latent rows");
     // The arguments live in the kernarg segment, so every per-layer descriptor read is a scalar load from constant
     // memory.  (Through a global pointer the compiler must assume the kernel's own stores may alias the table and issues
     // VECTOR loads with a full wait in front of each layer's first operand fetch: two or three dependent L2 round trips.)
@@ -683,7 +739,7 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
                 float mean = 0.f;
                 for (int k = 0; k < K; ++k) mean += comp[k * 8 + c];
                 mean /= (float)K;
-                float* o = A.kstats + unit * 8;
+                float* o = A.kstats + unit * (EXT ? 12 : 8);
                 if (tid < 3) {
                     float var = 0.f;
                     for (int k = 0; k < K; ++k) { const float d = comp[k * 8 + c] - mean; var += d * d; }
@@ -691,12 +747,13 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
                     o[3 + tid] = sqrtf(var / (float)K) * (float)K / (float)(K - 1);
                     if (A.sqerr != nullptr) {                                  // the integrand of img2mse(rgb_mean, target), RUN:1028 / HLP:15
                         const float e = mean - A.gt[unit * 3 + tid];
-                        A.sqerr[unit * 3 + tid] = e * e;
+                        A.sqerr[unit * (EXT ? 6 : 3) + tid] = e * e;
                     }
                 } else {
                     o[6 + (tid - 3)] = mean;
                 }
             }
+            if constexpr (EXT) kstats_ext_epilogue(comp, K, wave, lane_id_opaque(), A.kstats + unit * 12, A.gt != nullptr ? A.gt + unit * 3 : nullptr, A.sqerr + unit * 6);
         }
         }
         __syncthreads();
@@ -1215,6 +1272,8 @@ static hipError_t launch_fwd_t(const FwdArgs& a, const NetTab& ht, int n_cu, int
     auto fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4>;
     if constexpr (TRAIN)
         if (a.flags & CFNERF_F_EPS_ROWS) fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4, true>;      // one latent row per ray / point
+    if constexpr (MODE == 0 && !Q4)
+        if (a.flags & CFNERF_F_KSTATS_EXT) fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, false, false, true>;      // kstats [N,12], sqerr [N,6] (the ABI refuses it with a stash or rows)
     const size_t lds = fwd_lds_bytes(W, ht.ha_sz, a.K);
     const int64_t units = (MODE == 0) ? a.N : (a.P + kTileM - 1) / kTileM;
     int grid = (int)std::min<int64_t>(units, (int64_t)n_cu * per_cu);
@@ -1250,7 +1309,7 @@ hipError_t launch_fused_fwd(const FwdArgs& a, const NetTab& ht, int mode, bool t
 template <int W>
 static hipError_t fwd_attrs_w(int ha, int* per_cu_out) {
     const size_t lds = fwd_lds_bytes(W, ha, kMaxK);      // the limit; a launch asks for what its K needs
-    const void* fns[16] = {
+    const void* fns[20] = {
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32, true>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_F32>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, false, PREC_F32>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32>),
@@ -1259,7 +1318,10 @@ static hipError_t fwd_attrs_w(int ha, int* per_cu_out) {
         // the latent-rows variants (CFNERF_F_EPS_ROWS)
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, true, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32, true, true>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32, false, true>),
-        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_BF16X3, false, true>)};
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_BF16X3, false, true>),
+        // the extended-K-statistics variants (CFNERF_F_KSTATS_EXT)
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_F32, false, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, false, false, true>),
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_BF16X3, false, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3, false, false, true>)};
     int per_cu = 2;
     for (const void* fn : fns) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

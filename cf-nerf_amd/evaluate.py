@@ -7,9 +7,14 @@ uncertainty maps of RUN:1117-1131, sparsification_plot HLP:382-438).
   prediction, the ``np.std * n/(n-1)`` uncertainty, mean disparity/depth are reduced INSIDE the fused kernel
   (32 B per pixel leave the chip instead of 20*K B), optionally on a row slice of the image so an image is
   tiled across ranks with no exchange.
+* ``render_uncertainty(stats="ext")`` / ``image_metrics``: the four numbers of the paper's tables (PSNR, NLL, AUSE of the colour and of
+  the depth uncertainty) from ONE launch per image (CFNERF_F_KSTATS_EXT: 48 + 24 B per pixel, + 12 B of ground truth, no per-K map),
+  with ``sparsification_curves`` / ``ause_fused`` as the device-side form of the reference's sparsification helper.
 """
 from __future__ import annotations
 
+
+import math
 
 import numpy as np
 import torch
@@ -40,14 +45,19 @@ def row_shard(H: int, rank: int, world: int):
     return r0, r0 + base + (1 if rank < rem else 0)
 
 
+# what travels in gather_rows: the maps of render_uncertainty, then those of stats="ext" (52 more bytes per pixel with ground truth)
+_ROW_KEYS = ("rgb_mean", "rgb_unc", "disp_mean", "depth_mean", "sq_err", "disp_unc", "depth_unc", "acc_mean", "acc_unc", "nll")
+
+
 def gather_rows(local: dict, H: int, world: int, rank: int, group=None, dst: int = 0):
     """The optional exchange of the row-tiled evaluation: every rank rendered rows ``row_shard(H, rank, world)`` of one
     image with ``render_uncertainty``; rank ``dst`` gets the full-image maps (``rgb_mean [H,W,3]``, ``rgb_unc``, ``disp_mean``,
     ``depth_mean``, and ``sq_err`` when present), the others ``None``.  32 B per pixel travel (20 MB for 800 x 800), once per image;
     the render itself needs no exchange.  Shards differ by at most one row: they are padded to the largest for ``all_gather``.
-    A gloo group (CPU tests, ranks sharing one GPU) is served through host copies."""
+    A gloo group (CPU tests, ranks sharing one GPU) is served through host copies.  The maps of ``stats="ext"`` (``disp_unc``,
+    ``depth_unc``, ``acc_mean``, ``acc_unc``, ``nll``) travel too when present; a gathered ``nll`` gives ``loss_nll`` as ``sq_err`` gives ``mse``."""
     import torch.distributed as dist
-    keys = [k for k in ("rgb_mean", "rgb_unc", "disp_mean", "depth_mean", "sq_err") if k in local]
+    keys = [k for k in _ROW_KEYS if k in local]
     hmax = max(row_shard(H, r, world)[1] - row_shard(H, r, world)[0] for r in range(world))
     via_host = dist.get_backend(group) == "gloo"
     out = {}
@@ -67,18 +77,41 @@ def gather_rows(local: dict, H: int, world: int, rank: int, group=None, dst: int
         return None
     if "sq_err" in out:
         out["mse"] = out["sq_err"].mean()
+    if "nll" in out:
+        out["loss_nll"] = out["nll"].mean()
     return out
+
+
+def kde_nll(rgb_map, gt):
+    """Per-pixel, per-channel integrand of the loss's negative log-likelihood (RUN:1034-1042) from per-K colours ``rgb_map [...,3,K]`` and
+    ``gt [...,3]``, in the dtype of ``rgb_map``: the TRAIN estimator - bandwidth from ``torch.std`` (unbiased) times ``n/(n-1)`` - not the
+    ``np.std * n/(n-1)`` of ``rgb_unc``.  What CFNERF_F_KSTATS_EXT evaluates inside the kernel; used here only where the per-K maps were
+    asked for anyway (``want_maps=True`` with ``gt``)."""
+    n = rgb_map.shape[-1]
+    h = (torch.std(rgb_map, -1) * n / (n - 1) * torch.pow(torch.tensor(0.8 / n), torch.tensor(-1 / 7)).to(rgb_map) + 1e-05)[..., None]
+    r1 = torch.exp(-((rgb_map - gt[..., None]) ** 2) / (2 * h * h))
+    r2 = torch.pow(torch.tensor(2 * math.pi), -1.5).to(rgb_map) / h
+    return -torch.log((r1 * r2).mean(-1) + 1e-05)
 
 
 @torch.no_grad()
 def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, lindisp=False, white_bkgd=False,
-                       rows=None, want_maps=False, t_vals=None, gt=None, **_ignored):
+                       rows=None, want_maps=False, t_vals=None, gt=None, stats="basic", **_ignored):
     """Eval render of rows ``rows=(r0, r1)`` (default: all) of the image seen from ``c2w`` with the reductions over the
     K latent samples fused into the kernel.  Returns a dict with ``rgb_mean [h,W,3]``, ``rgb_unc [h,W,3]``
     (= ``np.std(rgbs,-1) * n/(n-1)``, RUN:1129-1130), ``disp_mean [h,W]`` (RUN:1124), ``depth_mean [h,W]`` and, if
     ``want_maps``, the per-K ``rgb_map [h,W,3,K]``, ``disp_map``, ``depth_map`` as render() returns them.  With ``gt``
     (ground-truth colours of those rows, ``[h,W,3]``) the per-pixel squared error of the K-mean prediction is produced by the
-    same launch (``sq_err [h,W,3]``; ``mse`` = its mean = ``img2mse(rgb_mean, gt)``, RUN:1028)."""
+    same launch (``sq_err [h,W,3]``; ``mse`` = its mean = ``img2mse(rgb_mean, gt)``, RUN:1028).
+
+    ``stats="ext"`` (CFNERF_F_KSTATS_EXT; every key above keeps its bits) adds, from the same launch, ``disp_unc`` / ``depth_unc [h,W]`` -
+    the depth-uncertainty maps, same estimator as ``rgb_unc`` - and ``acc_mean`` / ``acc_unc [h,W]`` (accumulated opacity, RUN:449); with
+    ``gt`` also ``nll [h,W,3]``, the per-pixel integrand of the loss's KDE negative log-likelihood (RUN:1034-1042: the train estimator,
+    see ``kde_nll``), and ``loss_nll`` = its mean.  84 B per pixel stay on the device (48 + 24 + the 12 of ``gt``).  With ``want_maps``
+    the extended statistics still come from the kernel's ``kstats``; ``nll`` is then taken from the per-K maps that were asked for."""
+    if stats not in ("basic", "ext"):
+        raise ValueError(f"stats must be 'basic' or 'ext', got {stats!r}")
+    ext = stats == "ext"
     net = _unwrap(network_fn)
     dev = net.device
     r0, r1 = rows if rows is not None else (0, H)
@@ -90,19 +123,22 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
     packed = _pack_rays(H, W, focal, c2w=c2w, n=n, pixel0=r0 * W, ndc=ndc, near=near, far=far, device=dev)
     net._sync()
     eps = net.eval_eps()
-    flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
-    sq = None
+    flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_KSTATS_EXT if ext else 0)
+    sq = nll = None
     if want_maps:
         o = _render_fwd(net, packed, t_vals, None, eps, flags, kstats=True, entropy=False)
         kst = o['kstats']
         if gt is not None:
-            sq = (kst[:, 0:3] - gt.to(dev, torch.float32).reshape(n, 3)) ** 2
+            g = gt.to(dev, torch.float32).reshape(n, 3)
+            sq = (kst[:, 0:3] - g) ** 2
+            if ext:
+                nll = kde_nll(o['rgb_map'], g)
     else:
-        kst = torch.empty(n, 8, device=dev)
+        kst = torch.empty(n, 12 if ext else 8, device=dev)
         g = None
         if gt is not None:
             g = gt.to(dev, torch.float32).reshape(n, 3).contiguous()
-            sq = torch.empty(n, 3, device=dev)
+            sq = torch.empty(n, 6 if ext else 3, device=dev)
         L.check(L.lib().cfnerf_render_eval(net.handle, L.ptr(packed), L.ptr(t_vals), L.ptr(eps), n, S, K, flags, L.ptr(g), L.ptr(kst), L.ptr(sq),
                                            L.stream()), "cfnerf_render_eval")
     h = r1 - r0
@@ -110,8 +146,15 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
                depth_mean=kst[:, 7].reshape(h, W))
     if want_maps:
         out.update(rgb_map=o['rgb_map'].reshape(h, W, 3, K), disp_map=o['disp_map'].reshape(h, W, K), depth_map=o['depth_map'].reshape(h, W, K))
+    if ext:
+        out.update(disp_unc=kst[:, 8].reshape(h, W), depth_unc=kst[:, 9].reshape(h, W), acc_mean=kst[:, 10].reshape(h, W),
+                   acc_unc=kst[:, 11].reshape(h, W))
+        if sq is not None and nll is None:
+            sq, nll = sq[:, 0:3].contiguous(), sq[:, 3:6]           # (sq_err contiguous: ``mse`` then reduces exactly as in "basic")
     if sq is not None:
         out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
+    if nll is not None:
+        out.update(nll=nll.reshape(h, W, 3), loss_nll=nll.mean())
     return out
 
 
@@ -136,3 +179,62 @@ def ause(var_vec, err_vec, err_type='rmse'):
     uncertain pixels (HLP:414-416,424); AUSE as usually defined removes them, which is ``uncert_type='v'``."""
     o, v = sparsification_plot(var_vec, err_vec, uncert_type='v', err_type=err_type)
     return float(np.mean(v - o))
+
+
+def sparsification_curves(var_vec, err_vec, uncert_type='c', err_type='rmse'):
+    """``sparsification_plot`` (same arguments, same return) without its 200 device-to-host round trips: one sort of the errors, one of
+    the uncertainties, ONE fp64 cumulative sum over both orderings, the reference's 100 prefix lengths ``int((1 - r) * n)`` computed on
+    the host exactly as HLP:405-406 computes them, the 200 prefix means gathered on the device and ONE copy to the host.  Differs from
+    ``sparsification_plot`` only in that a prefix mean is accumulated in fp64 instead of fp32 (a prefix of length 0 is nan in both)."""
+    ratio_removed = np.linspace(0, 1, 100, endpoint=False)
+    n = len(err_vec)
+    counts = torch.tensor([int((1 - r) * n) for r in ratio_removed], dtype=torch.int64)
+    err_sorted, _ = torch.sort(err_vec)
+    _, idx = torch.sort(torch.sqrt(var_vec), descending=(uncert_type == 'c'))
+    both = torch.stack([err_sorted, err_vec[idx]]).double()
+    del err_sorted, idx
+    both.cumsum_(1)
+    counts = counts.to(both.device)
+    sums = both[:, (counts - 1).clamp_(min=0)]
+    means = torch.where(counts > 0, sums, torch.zeros_like(sums)) / counts         # (0 / 0 = nan: the mean of an empty prefix)
+    if err_type == 'rmse':
+        means = torch.sqrt(means)
+    curves = means.to(err_vec.dtype).cpu().numpy()
+    return curves[0], curves[1]
+
+
+def ause_fused(var_vec, err_vec, err_type='rmse'):
+    """``ause`` on ``sparsification_curves``: same ``uncert_type='v'`` (ascending sort of the uncertainty, head kept = the most uncertain
+    pixels REMOVED, AUSE as usually defined; the reference's ``'c'`` keeps them, see ``ause``)."""
+    o, v = sparsification_curves(var_vec, err_vec, uncert_type='v', err_type=err_type)
+    return float(np.mean(v - o))
+
+
+@torch.no_grad()
+def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, **render_kw):
+    """The per-view numbers of the paper's tables for the image seen from ``c2w`` against ``gt [H,W,3]`` (and ``gt_depth [H,W]``): one
+    ``render_uncertainty(stats="ext", gt=gt)`` launch - no per-K map exists anywhere - plus the sorts of ``ause_fused``.  Returns floats:
+
+    * ``mse``, ``psnr`` = ``mse2psnr(img2mse(rgb_mean, gt))`` (RUN:1028-1029), ``loss_nll`` (RUN:1042);
+    * ``ause_rgb_rmse`` / ``ause_rgb_mae``: uncertainty = mean over the channels of ``rgb_unc ** 2`` (a variance: the helpers take its
+      root), error = mean over the channels of the squared / absolute error of the K-mean colour, per pixel;
+    * with ``gt_depth``: ``ause_depth_rmse`` / ``ause_depth_mae`` from ``depth_mean`` and ``depth_unc ** 2`` likewise.
+
+    All AUSE figures use ``uncert_type='v'`` like ``ause`` (the most uncertain pixels are removed first; the reference's ``'c'`` keeps
+    them, HLP:414-416,424).  ``render_kw``: near, far, ndc, lindisp, white_bkgd, t_vals of ``render_uncertainty``."""
+    for k in ("rows", "want_maps", "stats", "gt"):
+        if k in render_kw:
+            raise TypeError(f"image_metrics renders the whole image with stats='ext' and its own gt: {k}= is not an argument")
+    r = render_uncertainty(H, W, focal, c2w, network_fn, gt=gt, stats="ext", **render_kw)
+    mse = r["mse"]
+    out = dict(mse=float(mse), psnr=float(-10. * torch.log(mse) / math.log(10.)), loss_nll=float(r["loss_nll"]))
+    var = (r["rgb_unc"] ** 2).mean(-1).reshape(-1)
+    sq = r["sq_err"]
+    out["ause_rgb_rmse"] = ause_fused(var, sq.mean(-1).reshape(-1), 'rmse')
+    out["ause_rgb_mae"] = ause_fused(var, torch.sqrt(sq).mean(-1).reshape(-1), 'mae')
+    if gt_depth is not None:
+        d = r["depth_mean"] - gt_depth.to(sq.device, torch.float32).reshape(H, W)
+        var = (r["depth_unc"] ** 2).reshape(-1)
+        out["ause_depth_rmse"] = ause_fused(var, (d * d).reshape(-1), 'rmse')
+        out["ause_depth_mae"] = ause_fused(var, d.abs().reshape(-1), 'mae')
+    return out

@@ -81,13 +81,18 @@ enum {
     CFNERF_F_WHITE_BKGD = 1 << 2,       /* raw2outputs(white_bkgd=True) RUN:451-452 */
     CFNERF_F_STASH      = 1 << 3,       /* keep activations for cfnerf_render_bwd (implies TRAIN); ONE stash per model: a later
                                            STASH forward replaces it and bumps cfnerf_model_stash_generation */
-    CFNERF_F_EPS_ROWS   = 1 << 4        /* eps holds one [K,4] row per work item - per RAY in cfnerf_render_fwd ([N,K,4]), per POINT
+    CFNERF_F_EPS_ROWS   = 1 << 4,       /* eps holds one [K,4] row per work item - per RAY in cfnerf_render_fwd ([N,K,4]), per POINT
                                            in cfnerf_network_fwd ([P,K,4]) - instead of one [K,4] for the launch: the reference draws
                                            fresh latents per netchunk (RUN:47-64,82; MOD:234,246), so a batch of several netchunks
                                            uses several latent sets.  Train branch only (cfnerf_render_eval refuses it).  With
                                            CFNERF_F_STASH the stash keeps the CALLER's eps pointer (no copy, no workspace growth):
                                            the rows buffer must stay alive and unchanged until the matching backward has been
                                            enqueued and has run, like a lent workspace */
+    CFNERF_F_KSTATS_EXT = 1 << 5        /* the metrics of the paper's tables from the same launch: kstats rows grow from 8 to 12 floats and
+                                           sqerr rows from 3 to 6 (layouts at cfnerf_render_fwd / cfnerf_render_eval).  Accepted by
+                                           cfnerf_render_eval and by cfnerf_render_fwd with kstats_opt (train or eval branch, without
+                                           CFNERF_F_STASH and without CFNERF_F_EPS_ROWS); every other entry point that takes flags refuses
+                                           it.  Without the flag every buffer shape and every output bit is what it was */
 };
 
 CFNERF_API int         cfnerf_version(void);
@@ -150,6 +155,10 @@ CFNERF_API int cfnerf_sample_points(const float* rays, const float* t_vals, cons
  *   raw_opt [N,S,K,4], weights_opt [N,S,K], pts_opt [N,S,3]    (NULL = not wanted)
  *   kstats_opt [N,8]  fused reductions over the K latent samples, what the evaluation loop derives from the
  *                     per-K maps at RUN:1122-1131: mean_K rgb (3) | np.std_K(rgb) * n/(n-1) (3) | mean_K disp | mean_K depth
+ *                     with CFNERF_F_KSTATS_EXT [N,12]: columns 0..7 as above, bit for bit, then
+ *                       8  uncertainty of disp      9  uncertainty of depth      (the depth-uncertainty maps of the paper's AUSE tables)
+ *                       10 mean_K of the accumulated opacity acc_map (RUN:449)    11 its uncertainty
+ *                     "uncertainty" is the estimator of columns 3..5: np.std over K (biased) * n/(n-1), RUN:1130
  *   entropy_out [1]   loss_entropy of MOD:286 (TRAIN only, may be NULL otherwise); with CFNERF_F_EPS_ROWS the point-weighted
  *                     mean over the launch (= the mean of the reference's per-netchunk values weighted by their points) */
 CFNERF_API int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, const float* t_rand,
@@ -162,7 +171,14 @@ CFNERF_API int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float
  * RUN:1117-1131: K-mean prediction, np.std * n/(n-1) uncertainty, mean disparity / depth) and the per-pixel integrand of
  * img2mse(rgb_mean, target) (RUN:1028, HLP:15), all reduced INSIDE the fused forward: only 32 (+12) bytes per pixel leave
  * the chip instead of 20*K.  Eval branch (fixed eps, no jitter).  kstats [N,8] as in cfnerf_render_fwd; gt_opt [N,3] and
- * sqerr_opt [N,3] = (K-mean rgb - gt)^2 go together or are both NULL.  eps is always [K,4]: CFNERF_F_EPS_ROWS is refused. */
+ * sqerr_opt [N,3] = (K-mean rgb - gt)^2 go together or are both NULL.  eps is always [K,4]: CFNERF_F_EPS_ROWS is refused.
+ * With CFNERF_F_KSTATS_EXT kstats is [N,12] (columns as in cfnerf_render_fwd) and sqerr_opt is [N,6]: columns 0..2 the squared error,
+ * bit for bit, columns 3..5 the per-channel integrand of the loss's negative log-likelihood (RUN:1034-1042) at that pixel,
+ *     h     = torch.std_K(rgb) * n/(n-1) * (0.8/n)^(-1/7) + 1e-5                       (torch.std: UNBIASED, then n/(n-1) on top)
+ *     nll_c = -log( mean_K[ exp(-(rgb_k - gt)^2 / (2 h^2)) ] * (2 pi)^(-1.5) / h + 1e-5 )
+ * whose mean over pixels and channels is loss_nll of cfnerf_loss_fwd_bwd.  This is the TRAIN loop's estimator with its quirk (the
+ * n/(n-1) factor applied to an already unbiased std); it is NOT the estimator of kstats columns 3..5 (np.std, biased, * n/(n-1)).
+ * 48 + 24 = 72 (+12 for gt) bytes per pixel instead of 20*K; evaluated with libm expf / logf in every flow-math mode. */
 CFNERF_API int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, const float* eps, int64_t N, int S, int K,
                        int flags, const float* gt_opt, float* kstats, float* sqerr_opt, cfnerf_stream s);
 
