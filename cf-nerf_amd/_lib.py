@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # CFNERF_LIB: development aid for same-box A/B runs of two builds of the SAME library (never a fallback)
 LIB_PATH = os.environ.get("CFNERF_LIB") or os.path.join(HERE, "libcfnerf_hip.so")
 
-F_TRAIN, F_LINDISP, F_WHITE_BKGD, F_STASH, F_EPS_ROWS, F_KSTATS_EXT = 1, 2, 4, 8, 16, 32
+F_TRAIN, F_LINDISP, F_WHITE_BKGD, F_STASH, F_EPS_ROWS, F_KSTATS_EXT, F_GEOMETRY = 1, 2, 4, 8, 16, 32, 64
 
 
 class Cfg(C.Structure):

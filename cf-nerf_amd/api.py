@@ -507,6 +507,29 @@ class NeRF_Flows(nn.Module):
             return raw, torch.zeros_like(raw)                        # MOD:223
         return raw, ent.reshape(1, 1, 1).expand(P, K, 1)             # MOD:291
 
+    # ---- sample (MOD:69-96): the density latents of a batch of points, geometry only -----------------
+    def sample(self, x, eps_alpha=None):
+        """``alpha_k [P,K,1]``: the pre-softplus density latent of every (point, latent sample) of the pre-embedded ``x [P, input_ch +
+        input_ch_views]`` (the view columns are not read) - trunk -> ``h_alpha`` -> density flow, what the reference's ``sample`` evidently
+        means (its colour half is commented out, and as shipped it calls the flows without ``is_test`` and cannot run).  The latents are
+        ``self.sample_alpha`` AS THEY ARE (MOD:78 does not zero the last one, unlike the eval branch of ``forward``) or an explicit
+        ``eps_alpha [K,1]``.  One CFNERF_F_GEOMETRY launch: the colour branch is not computed; every value has the bits of
+        ``forward(x, is_test=True)[0][..., 3]`` with the same density latents.  Inference only."""
+        if torch.is_grad_enabled() and self.flat.requires_grad:
+            raise RuntimeError("NeRF_Flows.sample is inference only (a geometry-only launch keeps no activations): call it under "
+                               "torch.no_grad(), or use forward() for a differentiable density")
+        _need_gpu(x, "x")
+        if x.shape[-1] != self.input_ch + self.input_ch_views:
+            raise ValueError(f"x must have {self.input_ch + self.input_ch_views} channels, got {x.shape[-1]}")
+        ea = self.sample_alpha if eps_alpha is None else eps_alpha
+        if tuple(ea.shape) != (self.K_samples, 1):
+            raise ValueError(f"eps_alpha must be [K,1] = [{self.K_samples},1], got {tuple(ea.shape)}")
+        self._sync()
+        eps = torch.zeros(self.K_samples, 4)
+        eps[:, 3:] = ea.detach().to("cpu", torch.float32)
+        xf = _f32c(x.reshape(-1, x.shape[-1]))
+        return _network_geometry(self, xf, eps.to(self.device)).unsqueeze(-1)
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value:
@@ -554,6 +577,17 @@ def _network_fwd(model, xf, eps, K, flags):
     L.check(L.lib().cfnerf_network_fwd(model.handle, L.ptr(xf), L.ptr(eps), xf.shape[0], K, flags, L.ptr(raw), L.ptr(ent), L.stream()),
             "cfnerf_network_fwd")
     return raw, ent
+
+
+def _network_geometry(model, xf, eps, out=None):
+    """cfnerf_network_fwd with CFNERF_F_GEOMETRY: the density latents ``[P,K]`` of the encoded points ``xf [P,90]`` for the ``[K,4]`` latents
+    ``eps`` (column 3 is read), into ``out`` or a new tensor."""
+    P, K = xf.shape[0], eps.shape[0]
+    if out is None:
+        out = torch.empty(P, K, device=xf.device)
+    L.check(L.lib().cfnerf_network_fwd(model.handle, L.ptr(xf), L.ptr(eps), P, K, L.F_GEOMETRY, L.ptr(out), None, L.stream()),
+            "cfnerf_network_fwd")
+    return out
 
 
 class _NetworkFn(torch.autograd.Function):
@@ -712,6 +746,47 @@ def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True,
          'entropy': torch.zeros(1, device=dev) if entropy else None}
     L.check(L.lib().cfnerf_render_fwd(model.handle, L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), L.ptr(z_vals), L.ptr(eps), N, S, K, flags,
                                       *(L.ptr(t) for t in o.values()), L.stream()), "cfnerf_render_fwd")
+    return o
+
+
+@torch.no_grad()
+def render_geometry(ray_batch, network_fn, t_vals=None, lindisp=False, z_vals=None, weights=False):
+    """Geometry of the packed rays ``ray_batch [N,11]`` (o3, d3, near, far, viewdir3; the view direction is not read) on the eval branch, in
+    ONE CFNERF_F_GEOMETRY launch that skips the colour branch: ``{"depth_map" [N,K], "disp_map" [N,K]}`` and, with ``weights``,
+    ``"weights" [N,S,K]`` - each with the bits ``render_rays`` gives it on the eval branch.  ``t_vals [S]`` defaults to the reference's
+    sample table; ``z_vals [N,S]`` are explicit depths (what a hierarchical coarse pass hands on): with them ``t_vals`` is not needed and
+    not read, whatever its length."""
+    net = _unwrap(network_fn)
+    _need_gpu(ray_batch, "ray_batch")
+    rays = _f32c(ray_batch)
+    if rays.dim() != 2 or rays.shape[1] != 11:
+        raise ValueError(f"ray_batch must be [N,11], got {tuple(rays.shape)}")
+    if t_vals is None and z_vals is None:
+        t_vals = t_vals_table(rays.device)
+    net._sync()
+    flags = L.F_GEOMETRY | (L.F_LINDISP if lindisp else 0)
+    o = _render_geometry_fwd(net, rays, t_vals, net.eval_eps(), flags, z_vals=None if z_vals is None else _f32c(z_vals), weights=weights)
+    out = {"depth_map": o["depth_map"], "disp_map": o["disp_map"]}
+    if weights:
+        out["weights"] = o["weights"]
+    return out
+
+
+def _render_geometry_fwd(model, rays, t_vals, eps, flags, z_vals=None, maps=True, raw=False, weights=False, pts=False, kstats=False):
+    """cfnerf_render_fwd with CFNERF_F_GEOMETRY (in ``flags``) into newly allocated outputs: ``disp_map`` / ``depth_map [N,K]`` (``maps``),
+    ``raw [N,S,K]`` (the density latent), ``weights [N,S,K]``, ``pts [N,S,3]``, ``kstats [N,6]``; an output not asked for is None."""
+    N, K = rays.shape[0], eps.shape[-2]
+    if z_vals is not None:
+        if z_vals.dim() != 2 or z_vals.shape[0] != N:
+            raise ValueError(f"z_vals must be [N,S] with N = {N} rays, got {tuple(z_vals.shape)}")
+        t_vals = None                       # explicit depths: the geometry-only kernel does not read the sample table (any length, or none)
+    S = z_vals.shape[1] if z_vals is not None else t_vals.shape[0]
+    dev = rays.device
+    new = lambda want, *shape: torch.empty(*shape, device=dev) if want else None
+    o = {'disp_map': new(maps, N, K), 'depth_map': new(maps, N, K), 'raw': new(raw, N, S, K), 'weights': new(weights, N, S, K),
+         'pts': new(pts, N, S, 3), 'kstats': new(kstats, N, 6)}
+    L.check(L.lib().cfnerf_render_fwd(model.handle, L.ptr(rays), L.ptr(t_vals), None, L.ptr(z_vals), L.ptr(eps), N, S, K, flags, None,
+                                      *(L.ptr(t) for t in o.values()), None, L.stream()), "cfnerf_render_fwd")
     return o
 
 

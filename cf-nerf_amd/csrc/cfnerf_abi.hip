@@ -134,9 +134,9 @@ static int finish_train_fwd(cfnerf_model* m, int grid, const float* eps, int64_t
 }
 
 // the fused forward of a ray launch, between the timing events of cfnerf_timing_enable
-static int timed_fused_fwd(cfnerf_model* m, const FwdArgs& a, bool train, hipStream_t st, int* grid) {
+static int timed_fused_fwd(cfnerf_model* m, const FwdArgs& a, bool train, hipStream_t st, int* grid, int mode = 0) {
     if (m->timing) HIPCHK(hipEventRecord(m->fr0[m->fwd_launches % kFwdRing], st));
-    HIPCHK(launch_fused_fwd(a, m->plan.tab, 0, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, grid));
+    HIPCHK(launch_fused_fwd(a, m->plan.tab, mode, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, grid));
     if (m->timing) { HIPCHK(hipEventRecord(m->fr1[m->fwd_launches % kFwdRing], st)); ++m->fwd_launches; }
     return CFNERF_OK;
 }
@@ -151,10 +151,24 @@ static int check_device(const cfnerf_model* m) {
     return CFNERF_OK;
 }
 
-// CFNERF_F_KSTATS_EXT widens the kstats / sqerr rows of the two render entry points; anywhere else it would be silently ignored
-static int refuse_kstats_ext(int flags, const char* who) {
-    if (flags & CFNERF_F_KSTATS_EXT)
+// Flags that only some entry points implement: CFNERF_F_KSTATS_EXT widens the kstats / sqerr rows of the two render entry points,
+// CFNERF_F_GEOMETRY selects the geometry-only launch of the three fused-forward entry points.  Anywhere else they would be silently
+// ignored: `allowed` holds those of them that `who` takes.
+static int refuse_mode_flags(int flags, int allowed, const char* who) {
+    if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_KSTATS_EXT (it widens kstats / sqerr of cfnerf_render_eval and cfnerf_render_fwd)", who);
+    if (flags & CFNERF_F_GEOMETRY & ~allowed)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_GEOMETRY (the geometry-only launch of cfnerf_network_fwd, cfnerf_render_fwd and cfnerf_render_eval)", who);
+    return CFNERF_OK;
+}
+
+// CFNERF_F_GEOMETRY is an eval-branch launch of its own kernel: no train branch, no stash, one latent set, its own [N,6] statistics
+static int check_geometry_flags(int flags) {
+    static const struct { int bit; const char* name; } bad[] = {{CFNERF_F_TRAIN, "CFNERF_F_TRAIN"}, {CFNERF_F_STASH, "CFNERF_F_STASH"},
+                                                                {CFNERF_F_EPS_ROWS, "CFNERF_F_EPS_ROWS"}, {CFNERF_F_KSTATS_EXT, "CFNERF_F_KSTATS_EXT"}};
+    for (const auto& b : bad)
+        if (flags & b.bit)
+            return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY is an eval-branch launch without the colour branch: it cannot be combined with %s", b.name);
     return CFNERF_OK;
 }
 
@@ -268,7 +282,7 @@ int cfnerf_embed(const float* x, int64_t P, int multires, float* out, cfnerf_str
 
 int cfnerf_sample_points(const float* rays, const float* t_vals, const float* t_rand, int flags, int64_t N, int S, float* z_vals,
                          float* pts, cfnerf_stream s) {
-    if (int rc = refuse_kstats_ext(flags, "cfnerf_sample_points")) return rc;
+    if (int rc = refuse_mode_flags(flags, 0, "cfnerf_sample_points")) return rc;
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
     if (N == 0) return CFNERF_OK;
     if (!rays || !t_vals || !z_vals) return fail(CFNERF_E_INVALID, "NULL argument");
@@ -291,10 +305,16 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
     if (N == 0) return CFNERF_OK;            // empty batch: nothing to do (buffers may be NULL)
     if (!rays || !eps || (!t_vals && !z_vals_opt)) return fail(CFNERF_E_INVALID, "NULL argument");
-    const bool maps = rgb_map && disp_map && depth_map;
-    if (!maps && (rgb_map || disp_map || depth_map)) return fail(CFNERF_E_INVALID, "rgb_map/disp_map/depth_map must be given together");
+    const bool geom = flags & CFNERF_F_GEOMETRY;
+    if (geom) {
+        if (int rc = check_geometry_flags(flags)) return rc;
+        if (rgb_map) return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY computes no colour: rgb_map must be NULL");
+        if ((disp_map == nullptr) != (depth_map == nullptr)) return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY: disp_map and depth_map must be given together");
+    }
+    const bool maps = geom ? (disp_map && depth_map) : (rgb_map && disp_map && depth_map);
+    if (!geom && !maps && (rgb_map || disp_map || depth_map)) return fail(CFNERF_E_INVALID, "rgb_map/disp_map/depth_map must be given together");
     if (!maps && !kstats_opt) return fail(CFNERF_E_INVALID, "either the per-K maps or kstats_opt must be requested");
-    if (kstats_opt && K < 2) return fail(CFNERF_E_INVALID, "kstats needs K >= 2 (std * n/(n-1))");
+    if (kstats_opt && K < 2) return fail(CFNERF_E_INVALID, "kstats needs K >= 2 (std * n/(n-1))%s", geom ? " - also the [N,6] rows of CFNERF_F_GEOMETRY" : "");
     hipStream_t st = (hipStream_t)s;
     if (int rc = train_flags(flags, entropy_out)) return rc;
     if (flags & CFNERF_F_KSTATS_EXT) {
@@ -326,7 +346,12 @@ int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, 
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
     if (N == 0) return CFNERF_OK;
     if (!rays || !eps || !t_vals || !kstats) return fail(CFNERF_E_INVALID, "NULL argument");
-    if (K < 2) return fail(CFNERF_E_INVALID, "kstats needs K >= 2 (std * n/(n-1))");
+    const bool geom = flags & CFNERF_F_GEOMETRY;
+    if (geom) {
+        if (int rc = check_geometry_flags(flags)) return rc;
+        if (gt_opt || sqerr_opt) return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY computes no colour: gt_opt and sqerr_opt must be NULL");
+    }
+    if (K < 2) return fail(CFNERF_E_INVALID, "kstats needs K >= 2 (std * n/(n-1))%s", geom ? " - also the [N,6] rows of CFNERF_F_GEOMETRY" : "");
     if ((gt_opt == nullptr) != (sqerr_opt == nullptr)) return fail(CFNERF_E_INVALID, "gt_opt and sqerr_opt must be given together");
     if (flags & (CFNERF_F_TRAIN | CFNERF_F_STASH)) return fail(CFNERF_E_INVALID, "cfnerf_render_eval is the eval branch only");
     if (flags & CFNERF_F_EPS_ROWS)
@@ -342,7 +367,7 @@ int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, 
 
 int cfnerf_sample_pdf(const float* rays, const float* t_vals, const float* t_rand, int flags, const float* weights, const float* u,
                       int64_t N, int S, int K, int N_importance, float* z_out, cfnerf_stream s) {
-    if (int rc = refuse_kstats_ext(flags, "cfnerf_sample_pdf")) return rc;
+    if (int rc = refuse_mode_flags(flags, 0, "cfnerf_sample_pdf")) return rc;
     if (N < 0 || S < 3 || K < 1 || N_importance < 1) return fail(CFNERF_E_INVALID, "bad N/S/K/N_importance (S >= 3)");
     if (S + N_importance > 1024) return fail(CFNERF_E_UNSUPPORTED, "S + N_importance must be <= 1024");
     if (N == 0) return CFNERF_OK;
@@ -354,7 +379,9 @@ int cfnerf_sample_pdf(const float* rays, const float* t_vals, const float* t_ran
 int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_t P, int K, int flags, float* raw,
                        float* entropy_out, cfnerf_stream s) {
     if (int rc = check_common(m, K)) return rc;
-    if (int rc = refuse_kstats_ext(flags, "cfnerf_network_fwd")) return rc;
+    const bool geom = flags & CFNERF_F_GEOMETRY;
+    if (geom) if (int rc = check_geometry_flags(flags)) return rc;
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_GEOMETRY, "cfnerf_network_fwd")) return rc;
     if (P < 0 || P > 0x7fffffff) return fail(CFNERF_E_INVALID, "bad P");
     if (P == 0) return CFNERF_OK;
     if (!x || !eps || !raw) return fail(CFNERF_E_INVALID, "NULL argument");
@@ -366,6 +393,7 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
     a.ent_partials = train ? m->d_ent_partials : nullptr;
     if (int rc = forward_args(m, a, flags, 1, (int)P, K, true)) return rc;      // points-mode stash: ONE "ray" of P samples
     int grid = 0;
+    if (geom) return timed_fused_fwd(m, a, false, st, &grid, 1);      // (timed like a ray launch: tools/ab_geometry.py)
     HIPCHK(launch_fused_fwd(a, m->plan.tab, 1, train, m->precision, m->n_cu, m->fwd_blocks_per_cu, st, &grid));
     return train ? finish_train_fwd(m, grid, eps, P, 1, K, flags, nullptr, entropy_out, st) : CFNERF_OK;
 }

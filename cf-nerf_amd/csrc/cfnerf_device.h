@@ -847,6 +847,30 @@ __device__ __forceinline__ void flows_fwd2(const f32x2 (&tp)[42], f32x2 (&z)[3],
 #undef CFN_TH
 }
 
+// ---- the density flow alone (CFNERF_F_GEOMETRY: geom_fwd_kernel, cfnerf_fwd.hip) ------------------------------------------------------
+// ta[12] = th[72 .. 84) of the layout above: alpha d1[f] | 4+ d2[f] | 8+ b[f].  Operation for operation the two `a` lines of
+// flows_fwd<false, FAST>: the density chain shares no value with the colour chain, so `a` leaves with the bits the full flows give it.
+template <bool FAST>
+__device__ __forceinline__ void flow_alpha_fwd(const float (&ta)[12], float& a) {
+    using M = Num<FAST>;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const float t = M::tanh(ta[4 + f] * a + ta[8 + f]);
+        a = ta[f] * t + a;
+    }
+}
+// ... and for TWO latent samples of a point on Num2, the parameters as the 6 register pairs tp[j] = (ta[2 j], ta[2 j + 1]): the `a` lines of flows_fwd2
+__device__ __forceinline__ void flow_alpha_fwd2(const f32x2 (&tp)[6], f32x2& a) {
+    using M = Num2;
+#define CFN_TA(j) pair_half(tp[(j) >> 1], (j) & 1)
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const f32x2 t = M::tanh(CFN_TA(4 + f) * a + CFN_TA(8 + f));
+        a = CFN_TA(f) * t + a;
+    }
+#undef CFN_TA
+}
+
 // ---- LDS-DMA helpers (the fp32 big-tile loader, the small-job kernel, the standalone composite kernels)
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 

@@ -781,6 +781,403 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
 #undef CFN_KARGS
 }
 
+// CFNERF_F_GEOMETRY: columns 2..5 of a ray's [6] statistics row from the ray's final comp[k] = (_ _ _ depth acc T disp _) - the wave-per-quantity
+// part of kstats_ext_epilogue for its columns 8..11, operation for operation (a copy, so that the EXT variants are compiled from what they were):
+// wave 0 the spread of the disparity, 1 of the depth, 2 mean and spread of the accumulated opacity.
+__device__ __forceinline__ void kstats_geom_epilogue(const float* comp, int K, int wave, int lane, float* __restrict__ ks) {
+    if (wave >= 3) return;
+    const float fK = (float)K;
+    const bool l0 = lane < K, l1 = lane + 64 < K;
+    const int c = wave == 0 ? 6 : (wave == 1 ? 3 : 4);
+    const float x0 = l0 ? comp[lane * 8 + c] : 0.f, x1 = l1 ? comp[(lane + 64) * 8 + c] : 0.f;
+    const float mean = comp_sum(x0 + x1) / fK;
+    const float d0 = l0 ? x0 - mean : 0.f, d1 = l1 ? x1 - mean : 0.f;
+    const float ss = comp_sum(d0 * d0 + d1 * d1);
+    const float unc = sqrtf(ss / fK) * fK / (float)(K - 1);
+    if (lane == 0) {
+        if (wave == 2) { ks[4] = mean; ks[5] = unc; }
+        else ks[2 + wave] = unc;
+    }
+}
+
+// CFNERF_F_GEOMETRY (eval branch): the fused forward with the colour half removed - sampling, encoding, trunk, the h_alpha head, the density
+// flow head, the K density flows and (ray mode) the composite's depth / accumulated-opacity sums.  No feature head, views layer, h_rgb head,
+// colour flow heads or colour flows: 114 560 of the 614 144 MACs per point at W = 256 and three quarters of the flow phase's transcendentals.
+// A kernel of its own (not a variant of fused_fwd_kernel: those are compiled from what they were).  Phases 1-3 and the h_alpha head are the
+// eval variants' calls on the same operands in the same order, the density chain shares no arithmetic with the colour chain and the library is
+// built without fp contraction, so every output is bit for bit the unflagged eval launch's:
+//   MODE 1  raw [P,K] = raw[..., 3] of the full launch;
+//   MODE 0  raw [N,S,K], weights, pts, depth / disp [N,K] as before and kstats [N,6] = columns 6..11 of a CFNERF_F_KSTATS_EXT row.
+template <int W, int MODE /*0 rays, 1 points*/, int PREC>
+__global__ __launch_bounds__(FwdCfg<W>::NTHR, 2)
+void geom_fwd_kernel(const FwdArgs A_, const NetTab T_) {
+#define CFN_PHASE_LOCALS(F)                                                                                                              \
+    [[maybe_unused]] const int HA = F(HA0), HLD = HA + 4, S = F(S0), K = F(K0), ic = F(ic0), icv = F(icv0), wave = F(wave0);               \
+    [[maybe_unused]] const int chunks_per_ray = (S + kTileM - 1) / kTileM, Dn = F(Dn0), skip_l = F(skip0);                                \
+    [[maybe_unused]] float* const rowinfo = hs + kTileM * HLD; /* [65][4]: x y z zval */                                                  \
+    [[maybe_unused]] float* const comp = rowinfo + 68 * 4 + 32 + 16; /* (the layout of fwd_lds_bytes) [comp_rows(K)][8]: _ _ _ depth acc T disp _ */ \
+    [[maybe_unused]] const float* __restrict__ const wp = F(wp0);                                                                          \
+    [[maybe_unused]] const __bf16* __restrict__ const wp16 = F(wp160)
+    (void)A_; (void)T_;
+#define CFN_KARGS const CFN_KCONST FwdKargs* kq_ = kernarg_fresh<FwdKargs>(); const CFN_KCONST FwdArgs& A = kq_->A; const CFN_KCONST NetTab& T = kq_->T
+#define CFN_PHASE_ARGS CFN_KARGS; CFN_PHASE_LOCALS(sgpr_fresh)
+    CFN_KARGS;
+    using C = FwdCfg<W>;
+    constexpr int LD = C::LD;
+    constexpr int kWv = C::NWV, kThr = C::NTHR;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int HA0 = T.ha_sz;
+    float* const act = smem;
+    float* const hs = act + kTileM * LD;
+
+    const int tid = threadIdx.x, lane = lane_id(), wave0 = wave_id();
+    const float* const wp0 = A.wp;
+    const __bf16* const wp160 = reinterpret_cast<const __bf16*>(A.wp16);
+    const int S0 = A.S, K0 = A.K;
+    const int ic0 = T.ic, icv0 = T.icv;
+    const int Dn0 = T.D, skip0 = T.skip;
+    const int64_t n_units = (MODE == 0) ? A.N : (A.P + kTileM - 1) / kTileM;
+    const float a_mean = A.flat[0], a_std = A.flat[1];
+
+    for (int64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        float ro[3], rd[3], nearv = 0.f, farv = 1.f, dnorm = 0.f;
+        CFN_PHASE_ARGS;
+        if (MODE == 0) {
+            const float* r = A.rays + unit * 11;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { ro[d] = r[d]; rd[d] = r[3 + d]; }
+            nearv = r[6]; farv = r[7];
+            dnorm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);   // torch.norm(rays_d) RUN:429
+            if (tid < K) {
+                float* c = comp + tid * 8;
+                c[3] = c[4] = 0.f; c[5] = 1.f;
+            }
+        }
+        const int n_chunks = (MODE == 0) ? chunks_per_ray : 1;
+        for (int chunk = 0; chunk < n_chunks; ++chunk) {
+            CFN_PHASE_ARGS;
+            const int64_t p0 = (MODE == 0) ? unit * (int64_t)S + (int64_t)chunk * kTileM : unit * (int64_t)kTileM;
+            const int rows_valid = (MODE == 0) ? min(kTileM, S - chunk * kTileM) : (int)min((int64_t)kTileM, A.P - p0);
+
+            // ---- 1. sampling along the ray (RUN:510-534), as in fused_fwd_kernel
+            if (MODE == 0) {
+                const float* const a_zin = A.z_in;
+                const float* const a_tv = A.t_vals;
+                const float* const a_tr = A.t_rand;
+                float* const a_pts = A.pts;
+                const int a_flags = A.flags;
+                fetched_together(a_zin, a_tv, a_tr, a_pts, a_flags);
+                if (tid <= kTileM) {
+                    const int s = chunk * kTileM + tid;
+                    float zv = 0.f, px = 0.f, py = 0.f, pz = 0.f;
+                    if (s < S) {
+                        const int64_t si = unit * (int64_t)S + s;
+                        // explicit depths: the sample table is NOT read (it may be NULL or shorter than S, include/cfnerf.h) - the condition is
+                        // wave-uniform and taken once around the three loads, which still leave together in front of one wait
+                        float tv0 = 0.f, tvp = 0.f, tvm = 0.f;
+                        if (a_zin == nullptr) { tv0 = a_tv[s]; tvp = a_tv[min(s + 1, S - 1)]; tvm = a_tv[max(s - 1, 0)]; }
+                        float trv = 0.f, zin = 0.f;
+                        if (a_tr != nullptr) trv = a_tr[si];
+                        if (a_zin != nullptr) zin = a_zin[si];
+                        if (a_zin != nullptr) {
+                            zv = zin;
+                        } else {
+                            const bool lind = (a_flags & CFNERF_F_LINDISP) != 0;
+                            const float zc = zlin_f(tv0, nearv, farv, lind);
+                            zv = zc;
+                            if (a_tr != nullptr) {                                                 // RUN:518-532
+                                const float upper = (s == S - 1) ? zc : 0.5f * (zlin_f(tvp, nearv, farv, lind) + zc);
+                                const float lower = (s == 0) ? zc : 0.5f * (zc + zlin_f(tvm, nearv, farv, lind));
+                                zv = lower + (upper - lower) * trv;
+                            }
+                        }
+                        px = ro[0] + rd[0] * zv; py = ro[1] + rd[1] * zv; pz = ro[2] + rd[2] * zv;  // RUN:534
+                        if (tid < kTileM && a_pts != nullptr) {
+                            float* o = a_pts + (unit * (int64_t)S + s) * 3;
+                            o[0] = px; o[1] = py; o[2] = pz;
+                        }
+                    }
+                    float* ri = rowinfo + tid * 4;
+                    ri[0] = px; ri[1] = py; ri[2] = pz; ri[3] = zv;
+                }
+                __syncthreads();
+            }
+            // biases and operand-table entries travel one phase ahead, as in fused_fwd_kernel; behind the last trunk layer comes the h_alpha head
+            float bias_n[C::NTW];
+            SubL tl_cur = kload(T.trunk[0]);
+            SubL tl_nxt = kload((1 < Dn) ? T.trunk[1] : T.ha);
+            const SubL tl_skip = kload(T.skipseg);
+            load_bias<C::NTW>(tl_cur, wave, kWv, wp, bias_n);
+            // ---- 2. positional encoding of the tile into act[:, 0:64) and its parking for the skip layer (registers / the scratch slot)
+            encode_tile<MODE, LD, PREC, kThr>(act, rowinfo, A.x, p0, rows_valid, ic, icv);
+            constexpr bool kParkRegs = MODE == 0 && PREC == PREC_F32;
+            constexpr int kParkN = kTileM * 16 / kThr;
+            f32x4 park[kParkRegs ? kParkN : 1];
+            float* enc_park = (MODE == 0 && !kParkRegs) ? A.enc_scratch + (size_t)blockIdx.x * (kTileM * 64) : nullptr;
+            if (kParkRegs) {
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < kParkN; ++i) {
+                    const int idx = tid + i * kThr, row = idx >> 4, q = idx & 15;
+                    park[i] = *reinterpret_cast<const f32x4*>(act + row * LD + 4 * q);
+                }
+            } else if (MODE == 0) {
+                __syncthreads();
+                for (int idx = tid; idx < kTileM * 16; idx += kThr) {
+                    const int row = idx >> 4, q = idx & 15;
+                    if (row < rows_valid) {
+                        f32x4 v;
+                        const float* src = act + row * LD;
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) v[c] = act_load<PREC>(src, LD, 4 * q + c);
+                        *reinterpret_cast<f32x4*>(enc_park + row * 64 + 4 * q) = v;
+                    }
+                }
+            }
+            __syncthreads();
+            // ---- 3. trunk: D x (Linear + ReLU), skip concat after layer D/2   (MOD:168-172)
+            for (int l = 0; l < Dn; ++l) {
+                CFN_PHASE_ARGS;
+                f32x16 acc[2][C::NTW];
+                const SubL tl_nn = kload((l + 2 < Dn) ? T.trunk[l + 2] : T.ha);
+                acc_init(acc, bias_n);
+                asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[0][C::NTW - 1][0]) : "memory");
+                if (l + 1 < Dn) load_bias<C::NTW>(tl_nxt, wave, kWv, wp, bias_n);                  // (the h_alpha head adds its bias after the k-split sum)
+                mma_any<C::NTW, PREC, 2>(acc, tl_cur, wave, kWv, wp, wp16, act, LD);
+                asm volatile("" :: "s"(tl_nn.w16_off));
+                if (l >= 1 && l - 1 == skip_l) {
+                    __syncthreads();                 // every wave is done reading h_{l-1}
+                    if (kParkRegs) {
+#pragma unroll
+                        for (int i = 0; i < kParkN; ++i) {
+                            const int idx = tid + i * kThr, row = idx >> 4, q = idx & 15;
+                            *reinterpret_cast<f32x4*>(act + row * LD + 4 * q) = park[i];
+                        }
+                    } else if (MODE == 0) {
+                        for (int idx = tid; idx < kTileM * 16; idx += kThr) {
+                            const int row = idx >> 4, q = idx & 15;
+                            f32x4 v; v[0] = v[1] = v[2] = v[3] = 0.f;           // rows past a ragged tile: finite filler
+                            if (row < rows_valid) v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(enc_park + row * 64 + 4 * q));
+                            float* dstl = act + row * LD;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) act_store<PREC>(dstl, LD, 4 * q + c, v[c]);
+                        }
+                    } else {
+                        encode_tile<MODE, LD, PREC, kThr>(act, rowinfo, A.x, p0, rows_valid, ic, icv);
+                    }
+                    __syncthreads();
+                    mma_any<C::NTW, PREC, 2>(acc, tl_skip, wave, kWv, wp, wp16, act, LD);
+                }
+                __syncthreads();
+                store_tiles<C::NTW, ACT_RELU, PREC, false, false, true>(acc, tl_cur, wave, kWv, wp, act, LD, 0, nullptr, W, rows_valid);
+                __syncthreads();
+                tl_cur = tl_nxt; tl_nxt = tl_nn;
+            }
+            const SubL s_ha = tl_cur;                // after the last layer: the h_alpha head's entry
+
+            // ---- 4. the h_alpha head alone (MOD:175): K split over the waves, the partial tiles summed through act[] in the order of
+            //         fused_fwd_kernel (pp[0], q = 1 .. nparts-1, the bias) into hs
+            {
+                CFN_PHASE_ARGS;
+                f32x16 accA[2][1];
+                acc_zero(accA);
+                mma_ksplit<PREC, 2>(accA, s_ha, wave, kWv, wp, wp16, act, LD);
+                __syncthreads();                     // every wave is done reading h
+                {
+                    const int lo = lane_id_opaque();
+                    float* lp = act + (4 * (lo >> 5)) * LD + 32 * wave + (lo & 31);      // raw fp32 partial of wave w: act[:, 32w..32w+32)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) lp[(i * 32 + (r & 3) + 8 * (r >> 2)) * LD] = accA[i][0][r];
+                }
+                __syncthreads();
+                {
+                    const int ntc = (int)s_ha.nt, nparts = kWv / ntc;
+                    if (kThr % HA == 0) {
+                        const int c = tid % HA, rstep = kThr / HA;
+                        const float bc = wp[s_ha.b_off + c];
+                        const float* pp0 = act + 32 * (c >> 5) + (c & 31);                   // wave w = part * ntc + n-tile
+                        for (int row = tid / HA; row < kTileM; row += rstep) {
+                            const float* pp = pp0 + row * LD;
+                            float v = pp[0];
+                            for (int q = 1; q < nparts; ++q) v += pp[32 * ntc * q];
+                            v += bc;
+                            act_store<PREC>(hs + row * HLD, HLD, c, v);
+                        }
+                    } else {
+                        for (int idx = tid; idx < kTileM * HA; idx += kThr) {
+                            const int row = idx / HA, c = idx - row * HA;
+                            const float* pp = act + row * LD + 32 * (c >> 5) + (c & 31);
+                            float v = pp[0];
+                            for (int q = 1; q < nparts; ++q) v += pp[32 * ntc * q];
+                            v += wp[s_ha.b_off + c];
+                            act_store<PREC>(hs + row * HLD, HLD, c, v);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            // ---- 7. the density flow head (MOD:366-383), once per point, on wave 0: theta_alpha -> act[:, kThetaRgb : kThetaRgb + 32)
+            {
+                CFN_PHASE_ARGS;
+                const SubL s_fa = kload(T.fa);
+                if (wave == 0) {
+                    f32x16 acc[2][1];
+                    acc_zero(acc);
+                    const int lo = lane_id_opaque();
+                    const int cl = lo & 31, rbase = 4 * (lo >> 5);
+                    const float bv = wp[s_fa.b_off + cl];                           // lands under the MFMAs
+                    mma_any<1, PREC, 2>(acc, s_fa, 0, kWv, wp, wp16, hs, HLD);
+                    const bool tanh_col = cl < 2 * 4;                               // diag_activation of d1, d2 (MOD:337-348)
+                    float* lp = act + rbase * LD + kThetaRgb + cl;                  // (h is dead: every wave passed the barrier above)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            float v = acc[i][0][r] + bv;
+                            if (tanh_col) v = tanhf(v);
+                            lp[(i * 32 + (r & 3) + 8 * (r >> 2)) * LD] = v;
+                        }
+                }
+                __syncthreads();
+            }
+            // ---- 8. the K density flows (+ in ray mode the composite's weights, depth and opacity sums): lane = sample (row), waves stride over k
+            {
+                CFN_PHASE_ARGS;
+                const float* const f_eps = A.eps;
+                float* const f_raw = A.raw;
+                float* const f_weights = A.weights;
+                const int f_flags = A.flags;
+                fetched_together(f_eps, f_raw, f_weights, f_flags);
+                const int row = lane_id_opaque();
+                const bool valid = row < rows_valid;
+                float zval = 0.f, dist = 0.f;
+                if (MODE == 0) {
+                    zval = rowinfo[row * 4 + 3];
+                    const int s = chunk * kTileM + row;
+                    const float dz = (s == S - 1) ? 1e1f : rowinfo[(row + 1) * 4 + 3] - zval;      // RUN:426-427
+                    dist = dz * dnorm;                                                             // RUN:429
+                }
+                // the point's 12 density-flow parameters stay in registers over the walk (the pairs of the two-latent path are formed from them)
+                float ta[12];
+                {
+                    const f32x4* tp = reinterpret_cast<const f32x4*>(act + row * LD + kThetaRgb);
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        const f32x4 v = tp[q];
+                        ta[q * 4 + 0] = v[0]; ta[q * 4 + 1] = v[1]; ta[q * 4 + 2] = v[2]; ta[q * 4 + 3] = v[3];
+                    }
+                }
+                auto flow_phase = [&](auto fast_tag) {
+                    constexpr bool FAST = decltype(fast_tag)::value;
+                    using M = Num<FAST>;
+                    auto one = [&](const int k) {
+                        float a = f_eps[k * 4 + 3] * a_std + a_mean;                                   // MOD:200
+                        flow_alpha_fwd<FAST>(ta, a);
+                        if (f_raw != nullptr && valid) f_raw[(p0 + row) * (int64_t)K + k] = a;         // MOD:221, the density latent only
+                        if (MODE == 0) {
+                            const float sp_a = M::softplus(a);
+                            const float ea = valid ? M::exp(-sp_a * dist) : 1.f;
+                            const float alpha = 1.f - ea;                                              // RUN:424,442
+                            const float xk = (1.f - alpha) + 1e-10f;                                   // RUN:443
+                            float incl, excl;
+                            comp_scan_mul(xk, incl, excl);
+                            float* cp = comp + k * 8;
+                            const float Tcar = cp[5];
+                            const float wgt = alpha * (Tcar * excl);
+                            if (f_weights != nullptr && valid) f_weights[(p0 + row) * (int64_t)K + k] = wgt;
+                            const float sd = comp_sum(wgt * zval);                                     // RUN:447
+                            const float sa = comp_sum(wgt);                                            // RUN:449
+                            const float tot = comp_last(incl);
+                            if (lane == 0) { cp[3] += sd; cp[4] += sa; cp[5] = Tcar * tot; }
+                        }
+                    };
+                    auto two = [&](const int k0, const int k1) {
+                        using M2 = Num2;
+                        f32x2 a;
+                        { f32x2 ec; ec[0] = f_eps[k0 * 4 + 3]; ec[1] = f_eps[k1 * 4 + 3]; a = ec * a_std + a_mean; }
+                        f32x2 tp[6];
+#pragma unroll
+                        for (int j = 0; j < 6; ++j) { tp[j][0] = ta[2 * j]; tp[j][1] = ta[2 * j + 1]; }
+                        flow_alpha_fwd2(tp, a);
+                        if (f_raw != nullptr && valid) {
+                            f_raw[(p0 + row) * (int64_t)K + k0] = a[0];
+                            f_raw[(p0 + row) * (int64_t)K + k1] = a[1];
+                        }
+                        if (MODE == 0) {
+                            const f32x2 sp_a = M2::softplus(a);
+                            f32x2 ea = M2::exp(-sp_a * dist);
+                            if (!valid) ea = 1.f;
+                            const f32x2 alpha = 1.f - ea;
+                            const f32x2 xk = (1.f - alpha) + 1e-10f;
+                            f32x2 incl, excl;
+                            { float i0, x0, i1, x1; comp_scan_mul(xk[0], i0, x0); comp_scan_mul(xk[1], i1, x1); incl[0] = i0; incl[1] = i1; excl[0] = x0; excl[1] = x1; }
+                            float* cp0 = comp + k0 * 8; float* cp1 = comp + k1 * 8;
+                            f32x2 Tcar; Tcar[0] = cp0[5]; Tcar[1] = cp1[5];
+                            const f32x2 Tex = Tcar * excl;
+                            const f32x2 wgt = alpha * Tex;
+                            if (f_weights != nullptr && valid) {
+                                f_weights[(p0 + row) * (int64_t)K + k0] = wgt[0];
+                                f_weights[(p0 + row) * (int64_t)K + k1] = wgt[1];
+                            }
+                            const f32x2 wd = wgt * zval;
+#pragma unroll
+                            for (int c = 0; c < 2; ++c) {
+                                const float sd = comp_sum(wd[c]), sa = comp_sum(wgt[c]);
+                                const float tot = comp_last(incl[c]);
+                                float* cp = c ? cp1 : cp0;
+                                if (lane == 0) { cp[3] += sd; cp[4] += sa; cp[5] = Tcar[c] * tot; }
+                            }
+                        }
+                    };
+                    if constexpr (FAST) {
+                        int k = wave;
+                        for (; k + kWv < K; k += 2 * kWv) two(k, k + kWv);
+                        if (k < K) one(k);
+                    } else {
+                        for (int k = wave; k < K; k += kWv) one(k);
+                    }
+                };
+                const bool fast = (f_flags & CFNERF_F_FLOW_MATH_SET) ? (f_flags & CFNERF_F_FLOW_MATH_FAST) != 0 : K >= kFastFlowsK;     // wave-uniform
+                if (fast) flow_phase(std::true_type{});
+                else flow_phase(std::false_type{});
+            }
+            __syncthreads();
+        }  // chunks
+
+        {   // ---- 9. the ray's outputs
+        CFN_PHASE_ARGS;
+        if (MODE == 0 && tid < K) {
+            float* cp = comp + tid * 8;
+            const float depth = cp[3], acc = cp[4];
+            const float disp = 1.f / fmaxf(1e-10f + 1e-10f, depth / (acc + 1e-10f) + 1e-10f);                    // RUN:448
+            if (A.depth != nullptr) {
+                A.disp[unit * (int64_t)K + tid] = disp;
+                A.depth[unit * (int64_t)K + tid] = depth;
+            }
+            cp[6] = disp;
+        }
+        if (MODE == 0 && A.kstats != nullptr) {
+            // [N,6]: mean_K disp | mean_K depth (the serial sums of kstats columns 6, 7) | then kstats_geom_epilogue
+            __syncthreads();
+            if (tid < 2) {
+                const int c = tid == 0 ? 6 : 3;
+                float mean = 0.f;
+                for (int k = 0; k < K; ++k) mean += comp[k * 8 + c];
+                mean /= (float)K;
+                A.kstats[unit * 6 + tid] = mean;
+            }
+            kstats_geom_epilogue(comp, K, wave, lane_id_opaque(), A.kstats + unit * 6);
+        }
+        }
+        __syncthreads();
+    }  // units
+#undef CFN_PHASE_ARGS
+#undef CFN_PHASE_LOCALS
+#undef CFN_KARGS
+}
+
 // base-Gaussian log-densities of one [K,4] set of latents, summed over k (MOD:268,283: Normal(mean, std).log_prob of z0 = eps std + mean)
 __device__ __forceinline__ void base_logprob_sums(const float* eps, int K, const float* flat, float& base_a, float& base_r) {
     const float a_mean = flat[0], a_std = flat[1];
@@ -1295,7 +1692,31 @@ static hipError_t launch_fwd_w(const FwdArgs& a, const NetTab& ht, int mode, boo
     return train ? launch_fwd_t<W, 1, true, PREC_F32>(a, ht, n_cu, per_cu, st, grid_out) : launch_fwd_t<W, 1, false, PREC_F32>(a, ht, n_cu, per_cu, st, grid_out);
 }
 
+// CFNERF_F_GEOMETRY: the geometry-only kernel of (width, mode, precision); the ABI admits the flag on the eval branch only
+template <int W>
+static hipError_t launch_geom_w(const FwdArgs& a, const NetTab& ht, int mode, int prec, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
+    auto fn = geom_fwd_kernel<W, 0, PREC_F32>;
+    if (prec == PREC_BF16X3) fn = mode == 0 ? geom_fwd_kernel<W, 0, PREC_BF16X3> : geom_fwd_kernel<W, 1, PREC_BF16X3>;
+    else if (mode != 0) fn = geom_fwd_kernel<W, 1, PREC_F32>;
+    const size_t lds = fwd_lds_bytes(W, ht.ha_sz, a.K);
+    const int64_t units = (mode == 0) ? a.N : (a.P + kTileM - 1) / kTileM;
+    int grid = (int)std::min<int64_t>(units, (int64_t)n_cu * per_cu);
+    if (grid < 1) grid = 1;
+    if (grid_out) *grid_out = grid;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(FwdCfg<W>::NTHR), lds, st, a, ht);
+    return hipGetLastError();
+}
+
 hipError_t launch_fused_fwd(const FwdArgs& a, const NetTab& ht, int mode, bool train, int prec, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
+    if (a.flags & CFNERF_F_GEOMETRY) {
+        if (train) return hipErrorInvalidValue;
+        switch (ht.W) {
+#define CFN_W_CASE(w) case w: return launch_geom_w<w>(a, ht, mode, prec, n_cu, per_cu, st, grid_out);
+            CFN_FOR_EACH_WIDTH(CFN_W_CASE)
+#undef CFN_W_CASE
+        }
+        return hipErrorInvalidValue;
+    }
     switch (ht.W) {
 #define CFN_W_CASE(w) case w: return launch_fwd_w<w>(a, ht, mode, train, prec, n_cu, per_cu, st, grid_out);
         CFN_FOR_EACH_WIDTH(CFN_W_CASE)
@@ -1327,6 +1748,14 @@ static hipError_t fwd_attrs_w(int ha, int* per_cu_out) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         per_cu = std::min(per_cu, max_blocks_per_cu(fn, fwd_lds_bytes(W, ha, 16), FwdCfg<W>::NTHR));
+    }
+    // the geometry-only kernels (CFNERF_F_GEOMETRY): the same LDS tile and launch bounds, launched with the occupancy read above
+    const void* gfns[4] = {
+        reinterpret_cast<const void*>(geom_fwd_kernel<W, 0, PREC_F32>), reinterpret_cast<const void*>(geom_fwd_kernel<W, 1, PREC_F32>),
+        reinterpret_cast<const void*>(geom_fwd_kernel<W, 0, PREC_BF16X3>), reinterpret_cast<const void*>(geom_fwd_kernel<W, 1, PREC_BF16X3>)};
+    for (const void* fn : gfns) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
     }
     *per_cu_out = std::max(1, per_cu);
     return hipSuccess;

@@ -33,8 +33,8 @@ struct FwdArgs {
     int64_t N, P;             // rays, points (P = N*S in ray mode)
     int32_t S, K, flags;
     float *rgb_map, *disp, *depth;       // [N,3,K] [N,K] [N,K]
-    float *raw, *weights, *pts;          // optional [P,K,4] [P,K] [P,3]
-    float *kstats;                       // optional [N,8] fused K-statistics; CFNERF_F_KSTATS_EXT (flags, picks the kernel variant): [N,12]
+    float *raw, *weights, *pts;          // optional [P,K,4] [P,K] [P,3]; CFNERF_F_GEOMETRY (flags, picks geom_fwd_kernel): raw is [P,K], rgb_map is not written
+    float *kstats;                       // optional [N,8] fused K-statistics; CFNERF_F_KSTATS_EXT (flags, picks the kernel variant): [N,12]; CFNERF_F_GEOMETRY: [N,6]
     const float* gt;                     // optional [N,3] ground-truth colours (eval): with kstats, sqerr is written
     float* sqerr;                        // optional [N,3] (K-mean rgb - gt)^2 per pixel and channel; CFNERF_F_KSTATS_EXT: [N,6], + the NLL integrand
     float* ent_partials;                 // [grid,2]  (TRAIN)

@@ -10,6 +10,8 @@ uncertainty maps of RUN:1117-1131, sparsification_plot HLP:382-438).
 * ``render_uncertainty(stats="ext")`` / ``image_metrics``: the four numbers of the paper's tables (PSNR, NLL, AUSE of the colour and of
   the depth uncertainty) from ONE launch per image (CFNERF_F_KSTATS_EXT: 48 + 24 B per pixel, + 12 B of ground truth, no per-K map),
   with ``sparsification_curves`` / ``ause_fused`` as the device-side form of the reference's sparsification helper.
+* ``render_uncertainty(stats="geometry")`` / ``density_grid``: depth and disparity maps with their uncertainty, and density /
+  density-uncertainty volumes, from launches that skip the colour branch (CFNERF_F_GEOMETRY).
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .api import _pack_rays, _render_fwd, _unwrap, render, t_vals_table
+from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, render, t_vals_table
 
 
 def render_path_train(render_poses, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0):
@@ -46,6 +48,7 @@ def row_shard(H: int, rank: int, world: int):
 
 
 # what travels in gather_rows: the maps of render_uncertainty, then those of stats="ext" (52 more bytes per pixel with ground truth)
+# (stats="geometry" produces a subset of the same keys: depth_mean, disp_mean, depth_unc, disp_unc, acc_mean, acc_unc)
 _ROW_KEYS = ("rgb_mean", "rgb_unc", "disp_mean", "depth_mean", "sq_err", "disp_unc", "depth_unc", "acc_mean", "acc_unc", "nll")
 
 
@@ -108,9 +111,17 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
     the depth-uncertainty maps, same estimator as ``rgb_unc`` - and ``acc_mean`` / ``acc_unc [h,W]`` (accumulated opacity, RUN:449); with
     ``gt`` also ``nll [h,W,3]``, the per-pixel integrand of the loss's KDE negative log-likelihood (RUN:1034-1042: the train estimator,
     see ``kde_nll``), and ``loss_nll`` = its mean.  84 B per pixel stay on the device (48 + 24 + the 12 of ``gt``).  With ``want_maps``
-    the extended statistics still come from the kernel's ``kstats``; ``nll`` is then taken from the per-K maps that were asked for."""
-    if stats not in ("basic", "ext"):
-        raise ValueError(f"stats must be 'basic' or 'ext', got {stats!r}")
+    the extended statistics still come from the kernel's ``kstats``; ``nll`` is then taken from the per-K maps that were asked for.
+
+    ``stats="geometry"`` (CFNERF_F_GEOMETRY: the launch skips the colour branch) returns ``depth_mean``, ``disp_mean``, ``depth_unc``,
+    ``disp_unc``, ``acc_mean``, ``acc_unc [h,W]`` only - 24 B per pixel, each with the bits ``stats="ext"`` gives it; ``white_bkgd`` has no
+    effect on them, ``want_maps`` / ``gt`` are refused."""
+    if stats not in ("basic", "ext", "geometry"):
+        raise ValueError(f"stats must be 'basic', 'ext' or 'geometry', got {stats!r}")
+    if stats == "geometry":
+        if want_maps or gt is not None:
+            raise ValueError("stats='geometry' renders no colour: want_maps / gt are not arguments of it (api.render_geometry gives the per-K maps)")
+        return _render_uncertainty_geometry(H, W, focal, c2w, network_fn, near, far, ndc, lindisp, rows, t_vals)
     ext = stats == "ext"
     net = _unwrap(network_fn)
     dev = net.device
@@ -155,6 +166,79 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
         out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
     if nll is not None:
         out.update(nll=nll.reshape(h, W, 3), loss_nll=nll.mean())
+    return out
+
+
+def _render_uncertainty_geometry(H, W, focal, c2w, network_fn, near, far, ndc, lindisp, rows, t_vals):
+    """``render_uncertainty(stats="geometry")``: one cfnerf_render_eval launch with CFNERF_F_GEOMETRY, kstats [n,6]."""
+    net = _unwrap(network_fn)
+    dev = net.device
+    r0, r1 = rows if rows is not None else (0, H)
+    n, h = (r1 - r0) * W, r1 - r0
+    if t_vals is None:
+        t_vals = t_vals_table(dev)
+    packed = _pack_rays(H, W, focal, c2w=c2w, n=n, pixel0=r0 * W, ndc=ndc, near=near, far=far, device=dev)
+    net._sync()
+    kst = torch.empty(n, 6, device=dev)
+    flags = L.F_GEOMETRY | (L.F_LINDISP if lindisp else 0)
+    L.check(L.lib().cfnerf_render_eval(net.handle, L.ptr(packed), L.ptr(t_vals), L.ptr(net.eval_eps()), n, t_vals.shape[0], net.K_samples, flags,
+                                       None, L.ptr(kst), None, L.stream()), "cfnerf_render_eval")
+    keys = ("disp_mean", "depth_mean", "disp_unc", "depth_unc", "acc_mean", "acc_unc")
+    return {k: kst[:, i].reshape(h, W) for i, k in enumerate(keys)}
+
+
+def sigma_stats(alpha):
+    """Density statistics over the K latent samples (last axis) of the density latents ``alpha [...,K]``: sigma = softplus(alpha_k) (RUN:424),
+    its mean and ``np.std * n/(n-1)`` (RUN:1130, the estimator of every other uncertainty map here).  Returns ``(sigma_mean, sigma_unc)``."""
+    K = alpha.shape[-1]
+    sigma = torch.nn.functional.softplus(alpha)
+    return sigma.mean(-1), sigma.std(-1, unbiased=False) * K / (K - 1)
+
+
+@torch.no_grad()
+def density_grid(network_fn, lo, hi, res, chunk=1 << 20, eps_alpha=None, return_raw=False):
+    """Density and density-uncertainty volume on the axis-aligned grid of ``res = (X, Y, Z)`` points from corner ``lo`` to corner ``hi``
+    (both included), queried ``chunk`` points at a time with geometry-only launches (``NeRF_Flows.sample``'s kernel: no colour branch).
+    Returns ``{"sigma_mean", "sigma_unc"}`` ``[X,Y,Z]`` (``sigma_stats`` over K; K >= 2) and, with ``return_raw``, ``"alpha" [X,Y,Z,K]``, the
+    pre-softplus density latents.  Eval latents (``eval_eps()``: the last one zeroed) unless ``eps_alpha [K,1]`` is given."""
+    net = _unwrap(network_fn)
+    dev = net.device
+    K = net.K_samples
+    if K < 2:
+        raise ValueError("density_grid needs K_samples >= 2 (std * n/(n-1))")
+    X, Y, Z = (int(r) for r in res)
+    P = X * Y * Z
+    net._sync()
+    if eps_alpha is None:
+        eps = net.eval_eps()
+    else:
+        if tuple(eps_alpha.shape) != (K, 1):
+            raise ValueError(f"eps_alpha must be [K,1] = [{K},1], got {tuple(eps_alpha.shape)}")
+        eps = torch.zeros(K, 4)
+        eps[:, 3:] = eps_alpha.detach().to("cpu", torch.float32)
+        eps = eps.to(dev)
+    axes = [torch.linspace(float(lo[d]), float(hi[d]), n, device=dev) for d, n in enumerate((X, Y, Z))]
+    ic, icv = net.input_ch, net.input_ch_views
+    chunk = max(1, min(int(chunk), P))
+    xbuf = torch.zeros(chunk, ic + icv, device=dev)         # (the view columns are not read by the geometry-only launch)
+    emb = torch.empty(chunk, ic, device=dev)
+    abuf = torch.empty(chunk, K, device=dev)
+    mean, unc = torch.empty(P, device=dev), torch.empty(P, device=dev)
+    alpha = torch.empty(P, K, device=dev) if return_raw else None
+    lib = L.lib()
+    for p0 in range(0, P, chunk):
+        n = min(chunk, P - p0)
+        idx = torch.arange(p0, p0 + n, device=dev)
+        pts = torch.stack([axes[0][idx // (Y * Z)], axes[1][(idx // Z) % Y], axes[2][idx % Z]], -1).contiguous()
+        L.check(lib.cfnerf_embed(L.ptr(pts), n, (ic - 3) // 6, L.ptr(emb), L.stream()), "cfnerf_embed")
+        xbuf[:n, :ic] = emb[:n]
+        a = _network_geometry(net, xbuf[:n], eps, out=abuf[:n])
+        mean[p0:p0 + n], unc[p0:p0 + n] = sigma_stats(a)
+        if return_raw:
+            alpha[p0:p0 + n] = a
+    out = {"sigma_mean": mean.reshape(X, Y, Z), "sigma_unc": unc.reshape(X, Y, Z)}
+    if return_raw:
+        out["alpha"] = alpha.reshape(X, Y, Z, K)
     return out
 
 

@@ -88,11 +88,20 @@ enum {
                                            CFNERF_F_STASH the stash keeps the CALLER's eps pointer (no copy, no workspace growth):
                                            the rows buffer must stay alive and unchanged until the matching backward has been
                                            enqueued and has run, like a lent workspace */
-    CFNERF_F_KSTATS_EXT = 1 << 5        /* the metrics of the paper's tables from the same launch: kstats rows grow from 8 to 12 floats and
+    CFNERF_F_KSTATS_EXT = 1 << 5,       /* the metrics of the paper's tables from the same launch: kstats rows grow from 8 to 12 floats and
                                            sqerr rows from 3 to 6 (layouts at cfnerf_render_fwd / cfnerf_render_eval).  Accepted by
                                            cfnerf_render_eval and by cfnerf_render_fwd with kstats_opt (train or eval branch, without
                                            CFNERF_F_STASH and without CFNERF_F_EPS_ROWS); every other entry point that takes flags refuses
                                            it.  Without the flag every buffer shape and every output bit is what it was */
+    CFNERF_F_GEOMETRY   = 1 << 6        /* geometry only: the launch runs trunk -> h_alpha -> the density flow (and, for rays, the composite's
+                                           depth / opacity sums) and skips the colour branch - feature head, views layer, h_rgb head, colour
+                                           flows: 18.65 % of the dense work at W = 256 and three quarters of the flow phase.  Eval branch only:
+                                           refused together with CFNERF_F_TRAIN, CFNERF_F_STASH, CFNERF_F_EPS_ROWS or CFNERF_F_KSTATS_EXT.
+                                           Accepted by cfnerf_network_fwd (raw is [P,K], the density latent), cfnerf_render_fwd (rgb_map NULL,
+                                           raw_opt [N,S,K], kstats_opt [N,6]) and cfnerf_render_eval (kstats [N,6], no gt / sqerr); layouts at
+                                           those entry points.  What is written equals, bit for bit, the same quantity of the launch without
+                                           the flag.  Every other entry point that takes flags refuses it.  Without the flag every buffer
+                                           shape and every output bit is what it was */
 };
 
 CFNERF_API int         cfnerf_version(void);
@@ -160,7 +169,12 @@ CFNERF_API int cfnerf_sample_points(const float* rays, const float* t_vals, cons
  *                       10 mean_K of the accumulated opacity acc_map (RUN:449)    11 its uncertainty
  *                     "uncertainty" is the estimator of columns 3..5: np.std over K (biased) * n/(n-1), RUN:1130
  *   entropy_out [1]   loss_entropy of MOD:286 (TRAIN only, may be NULL otherwise); with CFNERF_F_EPS_ROWS the point-weighted
- *                     mean over the launch (= the mean of the reference's per-netchunk values weighted by their points) */
+ *                     mean over the launch (= the mean of the reference's per-netchunk values weighted by their points)
+ * With CFNERF_F_GEOMETRY (eval branch): rgb_map must be NULL; disp_map and depth_map [N,K] go together or are both NULL; raw_opt is
+ * [N,S,K], the density latent raw[..., 3] alone; weights_opt [N,S,K] and pts_opt as above; kstats_opt is [N,6] =
+ *     mean_K disp | mean_K depth | uncertainty of disp | uncertainty of depth | mean_K acc_map | its uncertainty
+ * - columns 6..11 of a CFNERF_F_KSTATS_EXT row, bit for bit (K >= 2).  z_vals_opt, CFNERF_F_LINDISP and t_rand behave as above;
+ * CFNERF_F_WHITE_BKGD is accepted and has no effect (it only touches colour).  Either the per-K maps or kstats_opt must be requested. */
 CFNERF_API int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, const float* t_rand,
                       const float* z_vals_opt, const float* eps, int64_t N, int S, int K, int flags,
                       float* rgb_map, float* disp_map, float* depth_map,
@@ -178,7 +192,9 @@ CFNERF_API int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float
  *     nll_c = -log( mean_K[ exp(-(rgb_k - gt)^2 / (2 h^2)) ] * (2 pi)^(-1.5) / h + 1e-5 )
  * whose mean over pixels and channels is loss_nll of cfnerf_loss_fwd_bwd.  This is the TRAIN loop's estimator with its quirk (the
  * n/(n-1) factor applied to an already unbiased std); it is NOT the estimator of kstats columns 3..5 (np.std, biased, * n/(n-1)).
- * 48 + 24 = 72 (+12 for gt) bytes per pixel instead of 20*K; evaluated with libm expf / logf in every flow-math mode. */
+ * 48 + 24 = 72 (+12 for gt) bytes per pixel instead of 20*K; evaluated with libm expf / logf in every flow-math mode.
+ * With CFNERF_F_GEOMETRY kstats is [N,6] (columns as in cfnerf_render_fwd: depth and disparity maps with their uncertainty, 24 bytes per
+ * pixel) and gt_opt / sqerr_opt must be NULL. */
 CFNERF_API int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, const float* eps, int64_t N, int S, int K,
                        int flags, const float* gt_opt, float* kstats, float* sqerr_opt, cfnerf_stream s);
 
@@ -194,7 +210,10 @@ CFNERF_API int cfnerf_sample_pdf(const float* rays, const float* t_vals, const f
  * (what batchify()/run_network hand to the model, RUN:47-64,82).  raw [P,K,4].  With CFNERF_F_STASH (implies TRAIN) the
  * activations are kept for cfnerf_network_bwd (the model's ONE stash, bound as one "ray" of P samples: size the workspace
  * with cfnerf_workspace_bytes(cfg, 1, P, K)).  eps [K,4]; with CFNERF_F_EPS_ROWS [P,K,4], one row per point (the
- * reference's netchunk boundaries are point boundaries).                                          */
+ * reference's netchunk boundaries are point boundaries).
+ * With CFNERF_F_GEOMETRY (eval branch; what NeRF_Flows.sample MOD:69-96 computes): x keeps its [P,90] stride and its view columns are not
+ * read; raw is [P,K], the pre-softplus density latent of every (point, latent) = raw[p,k,3] of the launch without the flag, bit for bit;
+ * entropy_out is ignored.                                                                          */
 CFNERF_API int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_t P, int K, int flags,
                        float* raw, float* entropy_out, cfnerf_stream s);
 
