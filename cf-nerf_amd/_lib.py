@@ -7,7 +7,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # CFNERF_LIB: development aid for same-box A/B runs of two builds of the SAME library (never a fallback)
 LIB_PATH = os.environ.get("CFNERF_LIB") or os.path.join(HERE, "libcfnerf_hip.so")
 
-F_TRAIN, F_LINDISP, F_WHITE_BKGD, F_STASH, F_EPS_ROWS, F_KSTATS_EXT, F_GEOMETRY = 1, 2, 4, 8, 16, 32, 64
+F_TRAIN, F_LINDISP, F_WHITE_BKGD, F_STASH, F_EPS_ROWS, F_KSTATS_EXT, F_GEOMETRY, F_INPUT_GRAD = 1, 2, 4, 8, 16, 32, 64, 128
+
+
+def input_grad_offset(n_params: int) -> int:
+    """x_off of include/cfnerf.h (CFNERF_F_INPUT_GRAD): where d_x starts in the grad_flat of cfnerf_network_bwd, in floats"""
+    return (n_params + 63) // 64 * 64
 
 
 class Cfg(C.Structure):

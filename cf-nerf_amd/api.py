@@ -51,6 +51,39 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------------------------
 # positional encoding (HLP:21-69).  Used only by the unfused run_network path and by callers that
 # want the embedding itself; the fused kernels encode on-chip.
+def _embed_fwd(x, multires, out_dim):
+    out = torch.empty(x.shape[0], out_dim, device=x.device)
+    L.check(L.lib().cfnerf_embed(L.ptr(x), x.shape[0], multires, L.ptr(out), L.stream()), "cfnerf_embed")
+    return out
+
+
+class _EmbedFn(torch.autograd.Function):
+    """Embedder.embed as an autograd node (the reference's is a torch graph, HLP:21-69): the cfnerf_embed kernel forward; the adjoint is a
+    few torch ops on the SAVED output, no second transcendental pass - with out = [x | sin(f_l x), cos(f_l x) ...],
+    d_in = d_out[:, :3] + sum_l f_l (cos_l d_sin_l - sin_l d_cos_l)."""
+
+    @staticmethod
+    def forward(ctx, x, multires, out_dim, freq_bands):
+        out = _embed_fwd(_f32c(x), multires, out_dim)
+        ctx.save_for_backward(out)
+        ctx.freq_bands = freq_bands
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (out,) = ctx.saved_tensors
+        return embed_backward(out, d_out, ctx.freq_bands), None, None, None
+
+
+def embed_backward(out, d_out, freq_bands):
+    """d loss / d inputs [P,3] of the positional encoding from its own output ``out [P, 3 + 6 L]`` and ``d_out`` (any device)"""
+    P, n = out.shape[0], freq_bands.numel()
+    o = out[:, 3:].reshape(P, n, 2, 3)                             # [:, l, 0] = sin(f_l x), [:, l, 1] = cos(f_l x)  (HLP:40-44)
+    g = d_out[:, 3:].reshape(P, n, 2, 3)
+    f = freq_bands.to(device=out.device, dtype=out.dtype)[None, :, None]
+    return d_out[:, :3] + ((o[:, :, 1] * g[:, :, 0] - o[:, :, 0] * g[:, :, 1]) * f).sum(1)
+
+
 class Embedder:
     def __init__(self, multires: int, input_dims: int = 3):
         self.multires = multires
@@ -62,9 +95,10 @@ class Embedder:
         _need_gpu(inputs, "Embedder input")                                           # HIP kernel only (cfnerf_embed)
         if inputs.shape[-1] != self.input_dims or self.input_dims != 3:
             raise ValueError("Embedder encodes 3-vectors (HLP:57-64: input_dims = 3)")
-        x = _f32c(inputs.reshape(-1, 3))
-        out = torch.empty(x.shape[0], self.out_dim, device=x.device)
-        L.check(L.lib().cfnerf_embed(L.ptr(x), x.shape[0], self.multires, L.ptr(out), L.stream()), "cfnerf_embed")
+        if torch.is_grad_enabled() and inputs.requires_grad:      # a learnable front end (pose, deformation ...) trains through the encoding
+            out = _EmbedFn.apply(inputs.reshape(-1, 3).to(torch.float32), self.multires, self.out_dim, self.freq_bands)
+        else:
+            out = _embed_fwd(_f32c(inputs.reshape(-1, 3)), self.multires, self.out_dim)
         return out.reshape(list(inputs.shape[:-1]) + [self.out_dim])
 
 
@@ -471,9 +505,9 @@ class NeRF_Flows(nn.Module):
         """One fresh train pair ``[K,4]`` on the device (latents.draw_pairs: the reference's order; the upload does not block the host)."""
         return LT.to_device(LT.draw_pairs(1, self.K_samples)[0], self.device)
 
-    def _one_call_only(self, is_test):
+    def _one_call_only(self, is_test, x=None):
         """True when a batch of points must reach forward() in ONE call, not in batchify's chunks."""
-        if torch.is_grad_enabled() and self.flat.requires_grad and not is_test:
+        if torch.is_grad_enabled() and ((self.flat.requires_grad and not is_test) or (x is not None and x.requires_grad)):
             # one launch = the model's one stash; chunks would each replace it and the backward would re-run their forwards
             return True
         # latent rows of the whole batch (render_rays' hand-over): its network calls are already in them
@@ -497,10 +531,16 @@ class NeRF_Flows(nn.Module):
         # (point rows from render_rays cover the whole batch: a network_query_fn of its own must hand all of it to ONE call)
         LT.check_rows(eps, P, "points", hint=": in netchunk mode render_rays hands one latent row per point of the whole batch, so a custom "
                                              "network_query_fn must evaluate all of them in one NeRF_Flows call")
-        if torch.is_grad_enabled() and self.flat.requires_grad and not is_test and P > 0:
+        want_x = torch.is_grad_enabled() and x.requires_grad
+        if ((torch.is_grad_enabled() and self.flat.requires_grad and not is_test) or want_x) and P > 0:
             # the reference's forward is an autograd graph (MOD:188-291): so is this one - cfnerf_network_fwd with the
-            # activation stash, differentiated by cfnerf_network_bwd (gradients reach the parameters; x is a constant)
-            raw, ent = _NetworkFn.apply(self.flat, self, xf, eps)
+            # activation stash, differentiated by cfnerf_network_bwd.  Gradients reach the parameters and - when x asks for
+            # one (CFNERF_F_INPUT_GRAD: a frozen network still gives x.grad) - the inputs.  The eval branch is a graph in the
+            # reference too: with an input gradient wanted it runs the same node on the eval latents.
+            xin = x.reshape(-1, x.shape[-1]).to(torch.float32) if want_x else xf
+            raw, ent = _NetworkFn.apply(self.flat, self, xin, eps)
+            if is_test:
+                return raw, torch.zeros_like(raw)                    # MOD:223
             return raw, ent.reshape(1, 1, 1).expand(P, K, 1)         # MOD:291
         raw, ent = _network_fwd(self, xf, eps, K, 0 if is_test else L.F_TRAIN)
         if is_test:
@@ -597,14 +637,17 @@ class _NetworkFn(torch.autograd.Function):
     have changed in between) and then differentiates: chunked callers train, at the price of one extra forward per chunk."""
 
     @staticmethod
-    def _forward_stash(model, xf, eps):
+    def _forward_stash(model, xf, eps, extra=0):
         K = eps.shape[-2]
         model.ensure_workspace(1, xf.shape[0], K)
-        return _network_fwd(model, xf, eps, K, L.F_TRAIN | L.F_STASH)
+        return _network_fwd(model, xf, eps, K, L.F_TRAIN | L.F_STASH | extra)
 
     @staticmethod
     def forward(ctx, flat, model, xf, eps):
-        raw, ent = _NetworkFn._forward_stash(model, xf, eps)
+        # xf asks for a gradient: the stash remembers CFNERF_F_INPUT_GRAD and the backward also writes d_x behind the parameter gradient
+        ctx.extra = L.F_INPUT_GRAD if ctx.needs_input_grad[2] else 0
+        xf = _f32c(xf)
+        raw, ent = _NetworkFn._forward_stash(model, xf, eps, ctx.extra)
         ctx.model, ctx.xf, ctx.eps, ctx.n_params = model, xf, eps, flat.numel()
         _mark_forward(ctx, model)
         return raw, ent.reshape(())
@@ -618,15 +661,21 @@ class _NetworkFn(torch.autograd.Function):
             # the stash is gone (a later grad-enabled forward replaced it): re-run the forward - the SAME forward, the parameters being the
             # ones it was taken at (checked above; a re-pack of unchanged parameters in between is harmless here)
             model._sync()
-            _NetworkFn._forward_stash(model, ctx.xf, ctx.eps)
+            _NetworkFn._forward_stash(model, ctx.xf, ctx.eps, ctx.extra)
             ctx.generation = lib.cfnerf_model_stash_generation(model.handle)
-        grad = torch.empty(ctx.n_params, device=model.flat.device)
         dr = _f32c(d_raw) if d_raw is not None else None
         de = _f32c(d_ent.reshape(1)) if d_ent is not None else None
         if dr is None and de is None:
-            return torch.zeros(ctx.n_params, device=model.flat.device), None, None, None
+            return torch.zeros(ctx.n_params, device=model.flat.device), None, (torch.zeros_like(ctx.xf) if ctx.extra else None), None
+        if not ctx.extra:
+            grad = torch.empty(ctx.n_params, device=model.flat.device)
+            L.check(lib.cfnerf_network_bwd(model.handle, ctx.generation, L.ptr(dr), L.ptr(de), L.ptr(grad), L.stream()), "cfnerf_network_bwd")
+            return grad, None, None, None
+        # CFNERF_F_INPUT_GRAD layout of grad_flat (cfnerf.h): [0, n_params) the parameter gradient, d_x [P, C] from x_off on
+        x_off, (P, Cx) = L.input_grad_offset(ctx.n_params), ctx.xf.shape
+        grad = torch.empty(x_off + P * Cx, device=model.flat.device)
         L.check(lib.cfnerf_network_bwd(model.handle, ctx.generation, L.ptr(dr), L.ptr(de), L.ptr(grad), L.stream()), "cfnerf_network_bwd")
-        return grad, None, None, None
+        return grad[:ctx.n_params], None, grad[x_off:].view(P, Cx), None
 
 
 def _composite_fwd(raw, z_vals, rays_d, white_bkgd):
@@ -694,7 +743,7 @@ def batchify(fn, chunk):
 
     def ret(inputs, is_val, is_test):
         m = getattr(fn, "module", fn)
-        if isinstance(m, NeRF_Flows) and m._one_call_only(is_test):
+        if isinstance(m, NeRF_Flows) and m._one_call_only(is_test, inputs):
             return fn(inputs, is_val, is_test)
         A, B = [], []
         for i in range(0, inputs.shape[0], chunk):

@@ -97,7 +97,7 @@ static int stash_bind(cfnerf_model* m, int64_t n, int s, int k) {
 // streams, the Q4 layout decision and a new generation (older backward passes are refused).
 static int forward_args(cfnerf_model* m, FwdArgs& a, int flags, int64_t n, int s, int K, bool points) {
     a.wp = m->d_packed; a.wp16 = m->d_packed16; a.flat = m->flat;
-    a.K = K; a.flags = (flags & 0xffff) | flow_math_bits(m);
+    a.K = K; a.flags = (flags & 0xffff & ~CFNERF_F_INPUT_GRAD) | flow_math_bits(m);      // (INPUT_GRAD is the backward's business: Stash::flags)
     if (!(flags & CFNERF_F_STASH)) return CFNERF_OK;
     if (int rc = stash_bind(m, n, s, K)) return rc;
     Stash& q = m->stash;
@@ -152,20 +152,23 @@ static int check_device(const cfnerf_model* m) {
 }
 
 // Flags that only some entry points implement: CFNERF_F_KSTATS_EXT widens the kstats / sqerr rows of the two render entry points,
-// CFNERF_F_GEOMETRY selects the geometry-only launch of the three fused-forward entry points.  Anywhere else they would be silently
-// ignored: `allowed` holds those of them that `who` takes.
+// CFNERF_F_GEOMETRY selects the geometry-only launch of the three fused-forward entry points, CFNERF_F_INPUT_GRAD asks the backward of
+// a cfnerf_network_fwd stash for d loss / d x.  Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_KSTATS_EXT (it widens kstats / sqerr of cfnerf_render_eval and cfnerf_render_fwd)", who);
     if (flags & CFNERF_F_GEOMETRY & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_GEOMETRY (the geometry-only launch of cfnerf_network_fwd, cfnerf_render_fwd and cfnerf_render_eval)", who);
+    if (flags & CFNERF_F_INPUT_GRAD & ~allowed)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_INPUT_GRAD (the input gradient of cfnerf_network_fwd with CFNERF_F_STASH, written by cfnerf_network_bwd)", who);
     return CFNERF_OK;
 }
 
 // CFNERF_F_GEOMETRY is an eval-branch launch of its own kernel: no train branch, no stash, one latent set, its own [N,6] statistics
 static int check_geometry_flags(int flags) {
     static const struct { int bit; const char* name; } bad[] = {{CFNERF_F_TRAIN, "CFNERF_F_TRAIN"}, {CFNERF_F_STASH, "CFNERF_F_STASH"},
-                                                                {CFNERF_F_EPS_ROWS, "CFNERF_F_EPS_ROWS"}, {CFNERF_F_KSTATS_EXT, "CFNERF_F_KSTATS_EXT"}};
+                                                                {CFNERF_F_EPS_ROWS, "CFNERF_F_EPS_ROWS"}, {CFNERF_F_KSTATS_EXT, "CFNERF_F_KSTATS_EXT"},
+                                                                {CFNERF_F_INPUT_GRAD, "CFNERF_F_INPUT_GRAD"}};
     for (const auto& b : bad)
         if (flags & b.bit)
             return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY is an eval-branch launch without the colour branch: it cannot be combined with %s", b.name);
@@ -303,6 +306,7 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
                       float* raw_opt, float* weights_opt, float* pts_opt, float* kstats_opt, float* entropy_out, cfnerf_stream s) {
     if (int rc = check_common(m, K)) return rc;
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_KSTATS_EXT | CFNERF_F_GEOMETRY, "cfnerf_render_fwd")) return rc;
     if (N == 0) return CFNERF_OK;            // empty batch: nothing to do (buffers may be NULL)
     if (!rays || !eps || (!t_vals && !z_vals_opt)) return fail(CFNERF_E_INVALID, "NULL argument");
     const bool geom = flags & CFNERF_F_GEOMETRY;
@@ -344,6 +348,7 @@ int cfnerf_render_eval(cfnerf_model* m, const float* rays, const float* t_vals, 
                        const float* gt_opt, float* kstats, float* sqerr_opt, cfnerf_stream s) {
     if (int rc = check_common(m, K)) return rc;
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_KSTATS_EXT | CFNERF_F_GEOMETRY, "cfnerf_render_eval")) return rc;
     if (N == 0) return CFNERF_OK;
     if (!rays || !eps || !t_vals || !kstats) return fail(CFNERF_E_INVALID, "NULL argument");
     const bool geom = flags & CFNERF_F_GEOMETRY;
@@ -381,7 +386,9 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
     if (int rc = check_common(m, K)) return rc;
     const bool geom = flags & CFNERF_F_GEOMETRY;
     if (geom) if (int rc = check_geometry_flags(flags)) return rc;
-    if (int rc = refuse_mode_flags(flags, CFNERF_F_GEOMETRY, "cfnerf_network_fwd")) return rc;
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_GEOMETRY | CFNERF_F_INPUT_GRAD, "cfnerf_network_fwd")) return rc;
+    if ((flags & CFNERF_F_INPUT_GRAD) && !(flags & CFNERF_F_STASH))
+        return fail(CFNERF_E_INVALID, "CFNERF_F_INPUT_GRAD needs CFNERF_F_STASH (d loss / d x is written by cfnerf_network_bwd from the stashed forward)");
     if (P < 0 || P > 0x7fffffff) return fail(CFNERF_E_INVALID, "bad P");
     if (P == 0) return CFNERF_OK;
     if (!x || !eps || !raw) return fail(CFNERF_E_INVALID, "NULL argument");

@@ -39,6 +39,17 @@ hipError_t launch_tail_bwd(const TailArgs& ta, int64_t n_rays, int ksplit, hipSt
 hipError_t launch_flows_bwd(const float* raw, const float* theta, const float* eps, int eps_rows, const float* flat, const float* d_raw,
                             const float* d_ent, int64_t P, int K, float* g_theta, float* gms_partials, unsigned* grid_out, hipStream_t st);
 
+// d loss / d x of a points-mode stash (CFNERF_F_INPUT_GRAD; cfnerf_inputgrad.hip): reads the final g_h / g_v and the flat weights
+struct InputGradArgs {
+    const float *g_h0, *g_h1, *g_v;                       // g_h[0], g_h[skip + 1] (null: a trunk without a skip concat), g_v; layout: q4
+    const float* flat;                                    // the caller's flat parameters (nn.Linear [out, in] row-major)
+    float* d_x;                                           // [P, ic + icv] row-major
+    int64_t P, n_tiles;
+    int32_t S, q4, ic, icv;
+    uint32_t w0_off, w1_off, wv_off;                      // flat offsets of W_pts0[0][0], W_pts(skip+1)[0][0], W_views0[0][W]
+};
+hipError_t launch_input_grad(const InputGradArgs& a, int W, int n_cu, hipStream_t st);
+
 // one 128 x 256 output tile of a weight-gradient job  dW[n][k] = sum_p dY[p][n] * X[p][k]
 struct DwTile {
     const float* dY; int32_t ldY, N, Npad;                // Npad: readable width of a dY row from the slice start

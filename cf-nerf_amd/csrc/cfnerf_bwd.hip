@@ -1374,6 +1374,22 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
                        q.bias_maps, (int)B.bias_maps.size(), grad_flat, accumulate);
     HIPCHK(hipGetLastError());
 
+    // ---- 2b. d loss / d x of a CFNERF_F_INPUT_GRAD stash: g_h and g_v are final here.  Outside the event pairs of the stages; it writes the
+    //      caller's buffer from x_off on (cfnerf.h) and only reads the workspace and the flat weights: the parameter gradient keeps its bits.
+    if (points && (q.flags & CFNERF_F_INPUT_GRAD)) {
+        const NetTab& T = m->plan.tab;
+        const bool has_skip = T.skip >= 0 && T.skip + 1 < T.D;       // the layer fed by cat([input_pts, h]) (MOD:171-172)
+        char key[64];
+        std::snprintf(key, sizeof key, "pts_linears.%d.weight", has_skip ? T.skip + 1 : 0);
+        InputGradArgs ia{};
+        ia.g_h0 = q.g_h; ia.g_h1 = has_skip ? q.g_h + (size_t)(T.skip + 1) * P * W : nullptr; ia.g_v = q.g_v;
+        ia.flat = m->flat; ia.d_x = grad_flat + (n_params + 63) / 64 * 64;
+        ia.P = P; ia.n_tiles = q.n_tiles; ia.S = q.S; ia.q4 = q.q4 ? 1 : 0; ia.ic = T.ic; ia.icv = T.icv;
+        ia.w0_off = (uint32_t)L.off("pts_linears.0.weight"); ia.w1_off = (uint32_t)L.off(key);
+        ia.wv_off = (uint32_t)(L.off("views_linears.0.weight") + W);
+        HIPCHK(launch_input_grad(ia, W, std::min(m->n_cu, kMaxCu), st));
+    }
+
     // ---- 3. weight gradients + reductions
     if (m->timing == 1) HIPCHK(hipEventRecord(m->ev0[3], st));
     if (!Hc.blocks.empty()) {

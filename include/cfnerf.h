@@ -93,7 +93,7 @@ enum {
                                            cfnerf_render_eval and by cfnerf_render_fwd with kstats_opt (train or eval branch, without
                                            CFNERF_F_STASH and without CFNERF_F_EPS_ROWS); every other entry point that takes flags refuses
                                            it.  Without the flag every buffer shape and every output bit is what it was */
-    CFNERF_F_GEOMETRY   = 1 << 6        /* geometry only: the launch runs trunk -> h_alpha -> the density flow (and, for rays, the composite's
+    CFNERF_F_GEOMETRY   = 1 << 6,       /* geometry only: the launch runs trunk -> h_alpha -> the density flow (and, for rays, the composite's
                                            depth / opacity sums) and skips the colour branch - feature head, views layer, h_rgb head, colour
                                            flows: 18.65 % of the dense work at W = 256 and three quarters of the flow phase.  Eval branch only:
                                            refused together with CFNERF_F_TRAIN, CFNERF_F_STASH, CFNERF_F_EPS_ROWS or CFNERF_F_KSTATS_EXT.
@@ -102,6 +102,17 @@ enum {
                                            those entry points.  What is written equals, bit for bit, the same quantity of the launch without
                                            the flag.  Every other entry point that takes flags refuses it.  Without the flag every buffer
                                            shape and every output bit is what it was */
+    CFNERF_F_INPUT_GRAD = 0x80          /* (= 1 << 7, bit 7) the matching cfnerf_network_bwd also writes d loss / d x, the gradient with respect to the
+                                           pre-embedded inputs (the reference's NeRF_Flows.forward is an autograd graph in x too: a learnable
+                                           front end - pose correction, deformation field, learned encoding - trains through it).  Accepted by
+                                           cfnerf_network_fwd only, and only together with CFNERF_F_STASH (the stash remembers it); refused with
+                                           CFNERF_F_GEOMETRY; combines freely with CFNERF_F_EPS_ROWS.  The backward of such a stash treats
+                                           grad_flat as [x_off + P * (input_ch + input_ch_views)] floats with
+                                               x_off = (cfnerf_param_count(cfg) + 63) / 64 * 64 :
+                                           [0, param_count) the parameter gradient, bit for bit what it is without the flag; d_x
+                                           [P, input_ch + input_ch_views] row-major from x_off; the floats in between are not written.
+                                           Every other entry point that takes flags refuses it.  Without the flag there is no extra launch and
+                                           every buffer shape and every output bit is what it was */
 };
 
 CFNERF_API int         cfnerf_version(void);
@@ -273,8 +284,11 @@ CFNERF_API int cfnerf_render_bwd_accumulate(cfnerf_model* m, uint64_t stash_gene
  *
  * replaces: loss.backward() through NeRF_Flows.forward for the cfnerf_network_fwd(... CFNERF_F_STASH ...) whose generation
  * is `stash_generation`.  d_raw [P,K,4] = d loss / d raw (NULL = zeros), d_entropy = ONE device float, d loss /
- * d loss_entropy (NULL = 0).  grad_flat [param_count] is OVERWRITTEN.  Gradients with respect to the inputs x are not
- * produced (the reference's sample points are not parameters).                                                         */
+ * d loss_entropy (NULL = 0).  grad_flat [param_count] is OVERWRITTEN.  If the forward carried CFNERF_F_INPUT_GRAD, grad_flat is
+ * [x_off + P * (input_ch + input_ch_views)] floats, x_off = (cfnerf_param_count(cfg) + 63) / 64 * 64: the parameter gradient in
+ * [0, param_count) as before, and d_x [P, input_ch + input_ch_views] = d loss / d x row-major from x_off (exact-fp32 MFMA in both
+ * precision modes, no atomics: bit-reproducible); the floats between param_count and x_off are not written.  Without that flag
+ * only [0, param_count) is touched.                                                                                      */
 CFNERF_API int cfnerf_network_bwd(cfnerf_model* m, uint64_t stash_generation, const float* d_raw, const float* d_entropy,
                        float* grad_flat, cfnerf_stream s);
 /* replaces: loss.backward() through raw2outputs(raw, z_vals, rays_d) RUN:411-454, stateless: the forward is recomputed from
