@@ -8,11 +8,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CFNERF_LIB") or os.path.join(HERE, "libcfnerf_hip.so")
 
 F_TRAIN, F_LINDISP, F_WHITE_BKGD, F_STASH, F_EPS_ROWS, F_KSTATS_EXT, F_GEOMETRY, F_INPUT_GRAD = 1, 2, 4, 8, 16, 32, 64, 128
+F_RAY_GRAD = 256
 
 
 def input_grad_offset(n_params: int) -> int:
     """x_off of include/cfnerf.h (CFNERF_F_INPUT_GRAD): where d_x starts in the grad_flat of cfnerf_network_bwd, in floats"""
     return (n_params + 63) // 64 * 64
+
+
+def ray_grad_offsets(n_params: int, N: int, S: int):
+    """(r_off, z_off, total) of include/cfnerf.h (CFNERF_F_RAY_GRAD), in floats: d_rays [N,11] starts at r_off and d_z [N,S] at z_off of the
+    grad_flat of cfnerf_render_bwd, which then holds ``total`` floats"""
+    r_off = (n_params + 63) // 64 * 64
+    z_off = r_off + (N * 11 + 63) // 64 * 64
+    return r_off, z_off, z_off + N * S
 
 
 class Cfg(C.Structure):

@@ -157,6 +157,81 @@ def _pack_rays(H, W, focal, c2w=None, rays=None, n=None, pixel0=0, ndc=False, ne
     return out
 
 
+def pack_rays_reference(H, W, focal, rays=None, c2w=None, ndc=False, near=0., far=1.):
+    """RUN:129-158 with get_rays (HLP:288-297) and ndc_rays (HLP:360-377, near = 1 as RUN:149 calls it) in plain torch, in the dtype and on
+    the device of its inputs: the closed form ``pack_rays`` differentiates (and what the CPU tests hold to the oracle).  ``[n,11]``."""
+    if c2w is not None:
+        dt, dev = c2w.dtype, c2w.device
+        i, j = torch.meshgrid(torch.arange(int(W), dtype=dt, device=dev), torch.arange(int(H), dtype=dt, device=dev), indexing="xy")
+        dirs = torch.stack([(i - W * .5) / focal, -(j - H * .5) / focal, -torch.ones_like(i)], -1)          # HLP:292
+        rays_d = torch.sum(dirs[..., None, :] * c2w[:3, :3], -1)                                             # HLP:294
+        rays_o = c2w[:3, -1].expand(rays_d.shape)                                                            # HLP:296
+    else:
+        rays_o, rays_d = rays
+    rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
+    viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)                                             # RUN:143 (before NDC)
+    if ndc:
+        t = -(1. + rays_o[..., 2]) / rays_d[..., 2]                                                          # HLP:362
+        rays_o = rays_o + t[..., None] * rays_d
+        cw, chh = -1. / (W / (2. * focal)), -1. / (H / (2. * focal))
+        oz = rays_o[..., 2]
+        o = torch.stack([cw * rays_o[..., 0] / oz, chh * rays_o[..., 1] / oz, 1. + 2. / oz], -1)             # HLP:366-368
+        d = torch.stack([cw * (rays_d[..., 0] / rays_d[..., 2] - rays_o[..., 0] / oz),
+                         chh * (rays_d[..., 1] / rays_d[..., 2] - rays_o[..., 1] / oz), -2. / oz], -1)       # HLP:370-372
+        rays_o, rays_d = o, d
+    one = torch.ones_like(rays_d[..., :1])
+    nr = near.reshape(-1, 1).to(one) if torch.is_tensor(near) else near * one                                # RUN:155
+    fr = far.reshape(-1, 1).to(one) if torch.is_tensor(far) else far * one
+    return torch.cat([rays_o, rays_d, nr, fr, viewdirs], -1)                                                 # RUN:156-158
+
+
+class _PackRaysFn(torch.autograd.Function):
+    """``pack_rays`` as an autograd node: the forward is the cfnerf_rays_setup kernel (the bits every launch reads), the backward the
+    closed form above differentiated by torch in fp32 on the device - a few elementwise ops per ray, once per step."""
+
+    @staticmethod
+    def forward(ctx, a, b, H, W, focal, from_pose, ndc, near, far):
+        ctx.cfg = (H, W, focal, from_pose, ndc, near, far)
+        ctx.save_for_backward(a, b) if not from_pose else ctx.save_for_backward(a)
+        if from_pose:
+            dev = a.device if a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+            with torch.cuda.device(dev):
+                return _pack_rays(H, W, focal, c2w=a, ndc=ndc, near=near, far=far, device=dev)
+        return _pack_rays(H, W, focal, rays=(a, b), ndc=ndc, near=near, far=far)
+
+    @staticmethod
+    def backward(ctx, d_packed):
+        H, W, focal, from_pose, ndc, near, far = ctx.cfg
+        leaves = [t.detach().to(d_packed.device, torch.float32).requires_grad_(True) for t in ctx.saved_tensors]
+        with torch.enable_grad():
+            out = pack_rays_reference(H, W, focal, c2w=leaves[0], ndc=ndc, near=near, far=far) if from_pose else \
+                pack_rays_reference(H, W, focal, rays=(leaves[0], leaves[1]), ndc=ndc, near=near, far=far)
+        g = torch.autograd.grad(out, leaves, d_packed.to(out.dtype))
+        g = [gi.to(t.device).reshape(t.shape) for gi, t in zip(g, ctx.saved_tensors)]
+        return (g[0], None if from_pose else g[1]) + (None,) * 7
+
+
+def pack_rays(H, W, focal, rays=None, c2w=None, ndc=False, near=0., far=1.):
+    """The packed ray batch ``[n,11]`` = o3, d3, near, far, viewdir3 that every launch reads (RUN:129-158), from explicit
+    ``rays=(rays_o, rays_d)`` or from a pose ``c2w [3,4]`` (all H x W pixels, row-major), DIFFERENTIABLE in them: the forward is the ray
+    set-up kernel with its unchanged bits; gradients reach ``rays_o`` / ``rays_d`` / ``c2w`` through ``get_rays``, the view-direction
+    normalisation and ``ndc_rays`` in closed form.  ``packed.backward(d_rays)`` chains a ``d_rays [n,11]`` (``render_rays``' gradient, or
+    ``train.Trainer(ray_grad=True).d_rays``) into a pose.  ``near`` / ``far``: numbers or per-ray tensors (constants)."""
+    if (rays is None) == (c2w is None):
+        raise ValueError("pack_rays takes either rays=(rays_o, rays_d) or c2w=")
+    if c2w is not None:
+        c2w = torch.as_tensor(c2w)
+        pose = c2w[:3, :4].to(torch.float32)
+        return _PackRaysFn.apply(pose, None, int(H), int(W), float(focal), True, bool(ndc), near, far)
+    _need_gpu(rays[1], "rays")
+    ro, rd = rays[0].reshape(-1, 3).to(torch.float32), rays[1].reshape(-1, 3).to(torch.float32)
+    return _PackRaysFn.apply(ro, rd, int(H), int(W), float(focal), False, bool(ndc), near, far)
+
+
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
+
+
 def get_rays(H, W, focal, c2w):
     """HLP:288-297 on the ray set-up kernel: ``rays_o, rays_d [H,W,3]`` on the GPU (of ``c2w`` if it lives on one, else the
     current device)."""
@@ -841,13 +916,22 @@ def _render_geometry_fwd(model, rays, t_vals, eps, flags, z_vals=None, maps=True
 
 class _RenderFn(torch.autograd.Function):
     """Fused render (forward with activation stash) + cfnerf_render_bwd.  The model has ONE stash: the node remembers
-    the generation of its forward and the backward is refused (loudly) if a later grad-enabled forward replaced it."""
+    the generation of its forward and the backward is refused (loudly) if a later grad-enabled forward replaced it.
+    When ``rays`` or an explicit ``z_vals`` asks for a gradient the stash carries CFNERF_F_RAY_GRAD and the backward also returns
+    ``d_rays [N,11]`` (columns 6, 7 - near / far - are zero: not computed, cfnerf.h) and ``d_z [N,S]``."""
 
     @staticmethod
     def forward(ctx, flat, model, rays, t_vals, t_rand, eps, flags, want_pts, z_vals):
         N, K = rays.shape[0], eps.shape[-2]
-        model.ensure_workspace(N, z_vals.shape[1] if z_vals is not None else t_vals.shape[0], K)
+        ctx.want_rays, ctx.want_z = ctx.needs_input_grad[2], z_vals is not None and ctx.needs_input_grad[8]
+        if ctx.want_rays or ctx.want_z:
+            flags |= L.F_RAY_GRAD
+        rays = _f32c(rays)
+        z_vals = None if z_vals is None else _f32c(z_vals)
+        S = z_vals.shape[1] if z_vals is not None else t_vals.shape[0]
+        model.ensure_workspace(N, S, K)
         o = _render_fwd(model, rays, t_vals, t_rand, eps, flags | L.F_STASH, z_vals, raw=True, pts=want_pts)
+        ctx.NS = (N, S)
         ctx.model = model
         ctx.eps = eps               # latent rows: the stash reads the caller's buffer until the backward (cfnerf.h, CFNERF_F_EPS_ROWS)
         ctx.n_params = flat.numel()
@@ -863,13 +947,19 @@ class _RenderFn(torch.autograd.Function):
         model = ctx.model
         _check_backward(ctx, model)                                # (a replaced STASH is refused by the library itself: generation id)
         dev = model.flat.device
-        grad = torch.empty(ctx.n_params, device=dev)
+        ray_grad = ctx.want_rays or ctx.want_z
+        # CFNERF_F_RAY_GRAD layout of grad_flat (cfnerf.h): the parameter gradient, then d_rays [N,11] from r_off and d_z [N,S] from z_off
+        (N, S), n = ctx.NS, ctx.n_params
+        r_off, z_off, total = L.ray_grad_offsets(n, N, S) if ray_grad else (n, n, n)
+        grad = torch.empty(total, device=dev)
         d_rgb = _f32c(d_rgb) if d_rgb is not None else torch.zeros(ctx.shape, device=dev)
         dd = _f32c(d_depth) if d_depth is not None else None
         de = _f32c(d_ent.reshape(1)) if d_ent is not None else None
         L.check(L.lib().cfnerf_render_bwd(model.handle, ctx.generation, L.ptr(d_rgb), L.ptr(dd), L.ptr(de), L.ptr(grad), L.stream()),
                 "cfnerf_render_bwd")
-        return grad, None, None, None, None, None, None, None, None
+        d_rays = grad[r_off:r_off + N * 11].view(N, 11) if ctx.want_rays else None
+        d_z = grad[z_off:z_off + N * S].view(N, S) if ctx.want_z else None
+        return (grad[:n] if ctx.needs_input_grad[0] else None), None, d_rays, None, None, None, None, None, d_z
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, uniformsample, retraw=False,
@@ -908,6 +998,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
         t_vals = t_vals.to(dev, torch.float32).contiguous()
     N, S, K = ray_batch.shape[0], t_vals.shape[0], model.K_samples
     rays = _f32c(ray_batch)
+    # the reference's render_rays is an autograd graph in the rays too (pose refinement, registration): the fused node differentiates it
+    want_rays = torch.is_grad_enabled() and ray_batch.requires_grad
     explicit = LT.pack(eps_alpha, eps_rgb)
     if is_train:
         # latents.train_latents: the mode's draws in the reference's order (a t_rand of the CPU generator included, unless there is one)
@@ -928,6 +1020,17 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
     fused = network_query_fn is None or getattr(network_query_fn, "_cfnerf_fused", False)
     if not fused:
         return _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_rand, eps, is_train, lindisp, white_bkgd)
+
+    if want_rays and fused and N > 0:
+        # CFNERF_F_RAY_GRAD: gradients reach ray_batch (columns 6, 7 - near / far - get zeros) whether or not the network is frozen.  The eval
+        # branch is a graph in the reference too: it runs the stashed train-branch launch on the fixed eval latents (no jitter unless asked
+        # for) and returns the eval structure, like NeRF_Flows.forward(is_test=True) with an input gradient wanted.
+        rgb_map, disp, depth, ent, raw, pts = _RenderFn.apply(model.flat, model, ray_batch.to(torch.float32), t_vals, t_rand, eps,
+                                                              flags | L.F_TRAIN, is_train, None)
+        if not is_train:
+            return {'rgb_map': rgb_map, 'disp_map': disp, 'depth_map': depth}
+        return {'rgb_map': rgb_map, 'disp_map': disp, 'depth_map': depth, 'raw': raw,
+                'loss_entropy': ent.reshape(1, 1, 1).expand(N * S, K, 1), 'pts': pts}
 
     if is_train and N > 0 and torch.is_grad_enabled() and model.flat.requires_grad:
         rgb_map, disp, depth, ent, raw, pts = _RenderFn.apply(model.flat, model, rays, t_vals, t_rand, eps, flags, True, None)
@@ -1028,7 +1131,11 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     """
     if not use_viewdirs:
         raise ValueError("use_viewdirs=False is not supported (the reference's model cannot run it, SURVEY R8)")
-    if c2w is not None:                          # a host pose goes into the kernel arguments as it is: no device round trip
+    if c2w_staticcam is None and (_wants_grad(c2w) if c2w is not None else _wants_grad(*rays)):
+        # a pose or rays that ask for a gradient (pose refinement, registration): the differentiable pack, then the fused node's ray gradient
+        sh = (H, W, 3) if c2w is not None else tuple(rays[1].shape)
+        packed = pack_rays(H, W, focal, rays=rays if c2w is None else None, c2w=c2w, ndc=ndc, near=near, far=far)
+    elif c2w is not None:                        # a host pose goes into the kernel arguments as it is: no device round trip
         dev = kwargs["network_fn"].module.device if hasattr(kwargs.get("network_fn"), "module") else _unwrap(kwargs["network_fn"]).device
         sh = (H, W, 3)
         packed = _pack_rays(H, W, focal, c2w=c2w, ndc=ndc and c2w_staticcam is None, near=near, far=far, device=dev)

@@ -97,7 +97,7 @@ static int stash_bind(cfnerf_model* m, int64_t n, int s, int k) {
 // streams, the Q4 layout decision and a new generation (older backward passes are refused).
 static int forward_args(cfnerf_model* m, FwdArgs& a, int flags, int64_t n, int s, int K, bool points) {
     a.wp = m->d_packed; a.wp16 = m->d_packed16; a.flat = m->flat;
-    a.K = K; a.flags = (flags & 0xffff & ~CFNERF_F_INPUT_GRAD) | flow_math_bits(m);      // (INPUT_GRAD is the backward's business: Stash::flags)
+    a.K = K; a.flags = (flags & 0xffff & ~(CFNERF_F_INPUT_GRAD | CFNERF_F_RAY_GRAD)) | flow_math_bits(m);      // (INPUT_GRAD / RAY_GRAD are the backward's business: Stash::flags)
     if (!(flags & CFNERF_F_STASH)) return CFNERF_OK;
     if (int rc = stash_bind(m, n, s, K)) return rc;
     Stash& q = m->stash;
@@ -153,7 +153,8 @@ static int check_device(const cfnerf_model* m) {
 
 // Flags that only some entry points implement: CFNERF_F_KSTATS_EXT widens the kstats / sqerr rows of the two render entry points,
 // CFNERF_F_GEOMETRY selects the geometry-only launch of the three fused-forward entry points, CFNERF_F_INPUT_GRAD asks the backward of
-// a cfnerf_network_fwd stash for d loss / d x.  Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
+// a cfnerf_network_fwd stash for d loss / d x, CFNERF_F_RAY_GRAD the backward of a cfnerf_render_fwd stash for d loss / d rays and d loss / d z_vals.
+// Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_KSTATS_EXT (it widens kstats / sqerr of cfnerf_render_eval and cfnerf_render_fwd)", who);
@@ -161,6 +162,8 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_GEOMETRY (the geometry-only launch of cfnerf_network_fwd, cfnerf_render_fwd and cfnerf_render_eval)", who);
     if (flags & CFNERF_F_INPUT_GRAD & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_INPUT_GRAD (the input gradient of cfnerf_network_fwd with CFNERF_F_STASH, written by cfnerf_network_bwd)", who);
+    if (flags & CFNERF_F_RAY_GRAD & ~allowed)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_RAY_GRAD (the ray gradient of cfnerf_render_fwd with CFNERF_F_STASH, written by cfnerf_render_bwd)", who);
     return CFNERF_OK;
 }
 
@@ -168,7 +171,7 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
 static int check_geometry_flags(int flags) {
     static const struct { int bit; const char* name; } bad[] = {{CFNERF_F_TRAIN, "CFNERF_F_TRAIN"}, {CFNERF_F_STASH, "CFNERF_F_STASH"},
                                                                 {CFNERF_F_EPS_ROWS, "CFNERF_F_EPS_ROWS"}, {CFNERF_F_KSTATS_EXT, "CFNERF_F_KSTATS_EXT"},
-                                                                {CFNERF_F_INPUT_GRAD, "CFNERF_F_INPUT_GRAD"}};
+                                                                {CFNERF_F_INPUT_GRAD, "CFNERF_F_INPUT_GRAD"}, {CFNERF_F_RAY_GRAD, "CFNERF_F_RAY_GRAD"}};
     for (const auto& b : bad)
         if (flags & b.bit)
             return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY is an eval-branch launch without the colour branch: it cannot be combined with %s", b.name);
@@ -306,7 +309,15 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
                       float* raw_opt, float* weights_opt, float* pts_opt, float* kstats_opt, float* entropy_out, cfnerf_stream s) {
     if (int rc = check_common(m, K)) return rc;
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
-    if (int rc = refuse_mode_flags(flags, CFNERF_F_KSTATS_EXT | CFNERF_F_GEOMETRY, "cfnerf_render_fwd")) return rc;
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_KSTATS_EXT | CFNERF_F_GEOMETRY | CFNERF_F_RAY_GRAD, "cfnerf_render_fwd")) return rc;
+    if (flags & CFNERF_F_RAY_GRAD) {
+        if (flags & CFNERF_F_GEOMETRY)
+            return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_GRAD cannot be combined with CFNERF_F_GEOMETRY (a geometry-only launch keeps no stash to differentiate)");
+        if (!(flags & CFNERF_F_STASH))
+            return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_GRAD needs CFNERF_F_STASH (d loss / d rays and d loss / d z_vals are written by cfnerf_render_bwd from the stashed forward)");
+        if (flags & CFNERF_F_KSTATS_EXT)
+            return fail(CFNERF_E_UNSUPPORTED, "CFNERF_F_RAY_GRAD cannot be combined with CFNERF_F_KSTATS_EXT (evaluation metrics: render without a stash)");
+    }
     if (N == 0) return CFNERF_OK;            // empty batch: nothing to do (buffers may be NULL)
     if (!rays || !eps || (!t_vals && !z_vals_opt)) return fail(CFNERF_E_INVALID, "NULL argument");
     const bool geom = flags & CFNERF_F_GEOMETRY;

@@ -50,6 +50,19 @@ struct InputGradArgs {
 };
 hipError_t launch_input_grad(const InputGradArgs& a, int W, int n_cu, hipStream_t st);
 
+// d loss / d rays, d loss / d z_vals of a ray stash (CFNERF_F_RAY_GRAD; cfnerf_raygrad.hip).  comp_zgrad reads the stash and the cotangents
+// after the tail stage; ray_grad reads the final g_h / g_v (ig: d_x, P, n_tiles unused) and the stashed encodings after backward-data
+struct RayGradArgs {
+    InputGradArgs ig;
+    const float *enc, *gd, *z, *rays, *raw, *at;          // the stash: gamma(p) [P,64], gamma(d) [P,32], z [P], rays [N,11], raw / at tile-transposed
+    const float *d_rgb, *d_depth;                         // cotangents [N,3,K], [N,K] or null
+    float *d_rays, *d_z;                                  // [N,11], [N,S] in the caller's grad_flat
+    int64_t N;
+    int32_t S, K, flags;
+};
+hipError_t launch_comp_zgrad(const RayGradArgs& a, hipStream_t st);
+hipError_t launch_ray_grad(const RayGradArgs& a, int W, int n_cu, hipStream_t st);
+
 // one 128 x 256 output tile of a weight-gradient job  dW[n][k] = sum_p dY[p][n] * X[p][k]
 struct DwTile {
     const float* dY; int32_t ldY, N, Npad;                // Npad: readable width of a dY row from the slice start

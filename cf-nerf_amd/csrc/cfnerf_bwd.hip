@@ -1359,6 +1359,18 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
     HIPCHK(hipGetLastError());
     if (m->timing == 1) HIPCHK(hipEventRecord(m->ev1[1], st));
 
+    // ---- 1b. CFNERF_F_RAY_GRAD: the composite's adjoint in z and |d| needs only the stash and the cotangents.  Outside the event pairs of the
+    //      stages; the ray blocks behind the parameter gradient (cfnerf.h) are per-launch quantities: overwritten, also by _accumulate.
+    const bool ray_grad = !points && (q.flags & CFNERF_F_RAY_GRAD);
+    RayGradArgs ra{};
+    if (ray_grad) {
+        const int64_t r_off = (n_params + 63) / 64 * 64, z_off = r_off + (N * 11 + 63) / 64 * 64;
+        ra.enc = q.enc; ra.gd = q.gd; ra.z = q.z; ra.rays = q.rays; ra.raw = q.raw; ra.at = q.at;
+        ra.d_rgb = d_out; ra.d_depth = d_depth_map; ra.d_rays = grad_flat + r_off; ra.d_z = grad_flat + z_off;
+        ra.N = N; ra.S = q.S; ra.K = q.K; ra.flags = q.flags;
+        HIPCHK(launch_comp_zgrad(ra, st));
+    }
+
     // ---- 2. fused backward-data (+ bias partials and their reduction: every bias gradient is final here)
     BwdArgs ba{};                                              // (q.dbp needs no memset: every launched workgroup starts its row on its first tile)
     ba.wp = m->d_packed; ba.wp16 = m->d_packed16; ba.P = P; ba.n_wg = n_wg; ba.nb = B.nb;
@@ -1376,18 +1388,24 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
 
     // ---- 2b. d loss / d x of a CFNERF_F_INPUT_GRAD stash: g_h and g_v are final here.  Outside the event pairs of the stages; it writes the
     //      caller's buffer from x_off on (cfnerf.h) and only reads the workspace and the flat weights: the parameter gradient keeps its bits.
-    if (points && (q.flags & CFNERF_F_INPUT_GRAD)) {
+    //      A CFNERF_F_RAY_GRAD ray stash takes the same product through the embedder and pts = o + d z, reduced per ray (ray_grad_kernel).
+    if (points ? (q.flags & CFNERF_F_INPUT_GRAD) != 0 : ray_grad) {
         const NetTab& T = m->plan.tab;
         const bool has_skip = T.skip >= 0 && T.skip + 1 < T.D;       // the layer fed by cat([input_pts, h]) (MOD:171-172)
         char key[64];
         std::snprintf(key, sizeof key, "pts_linears.%d.weight", has_skip ? T.skip + 1 : 0);
         InputGradArgs ia{};
         ia.g_h0 = q.g_h; ia.g_h1 = has_skip ? q.g_h + (size_t)(T.skip + 1) * P * W : nullptr; ia.g_v = q.g_v;
-        ia.flat = m->flat; ia.d_x = grad_flat + (n_params + 63) / 64 * 64;
+        ia.flat = m->flat; ia.d_x = points ? grad_flat + (n_params + 63) / 64 * 64 : nullptr;
         ia.P = P; ia.n_tiles = q.n_tiles; ia.S = q.S; ia.q4 = q.q4 ? 1 : 0; ia.ic = T.ic; ia.icv = T.icv;
         ia.w0_off = (uint32_t)L.off("pts_linears.0.weight"); ia.w1_off = (uint32_t)L.off(key);
         ia.wv_off = (uint32_t)(L.off("views_linears.0.weight") + W);
-        HIPCHK(launch_input_grad(ia, W, std::min(m->n_cu, kMaxCu), st));
+        if (points) {
+            HIPCHK(launch_input_grad(ia, W, std::min(m->n_cu, kMaxCu), st));
+        } else {
+            ra.ig = ia;
+            HIPCHK(launch_ray_grad(ra, W, std::min(m->n_cu, kMaxCu), st));
+        }
     }
 
     // ---- 3. weight gradients + reductions

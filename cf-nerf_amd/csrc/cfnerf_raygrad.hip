@@ -1,0 +1,210 @@
+// cfnerf_raygrad.hip - d loss / d rays and d loss / d z_vals of a cfnerf_render_fwd stash (CFNERF_F_RAY_GRAD), written by cfnerf_render_bwd
+// into the caller's grad_flat behind the parameter gradient (cfnerf.h: d_rays [N,11] from r_off, d_z [N,S] from z_off).  Two kernels that
+// only READ the stash, the cotangents and the flat parameters - the parameter gradient does not see them:
+//   comp_zgrad_kernel   after the tail stage: the composite's adjoint in z and |d| (RUN:424-447).  Writes d_z, d_rays[:, 3:6], zeroes the
+//                       other columns of d_rays.
+//   ray_grad_kernel<W>  after backward-data: the network's adjoint d loss / d gamma(p), d gamma(d) (the MFMA stage of input_grad_kernel,
+//                       cfnerf_igmma.h) taken through the embedder and the sampling line pts = o + d z (RUN:534) and reduced per ray.
+//                       Writes d_rays[:, 0:3] and [:, 8:11], adds to d_rays[:, 3:6] and to d_z.
+// Both walk a ray's chunks in a fixed order in ONE wave / ONE workgroup: no atomics, bit-reproducible run to run.
+#include <hip/hip_runtime.h>
+
+#include "cfnerf_kernels.h"
+#include "cfnerf_device.h"
+#include "cfnerf_bwd.h"
+#include "cfnerf_igmma.h"
+
+namespace cfnerf {
+
+// ------------------------------------------------------------------------------------------------
+// (a) One wave per ray, lane = sample, chunks of 64 walked back to front like tail_bwd_kernel, from the same tile-transposed raw / at
+//     pieces and with the same comp_adjoint_D recurrence.  Per (s, k), e = exp(-softplus(raw_3) dist), T from `at`, alpha = 1 - e, w = alpha T:
+//         g = sum_c G_c sigmoid(raw_c) + Gd z_s  (- sum_c G_c with WHITE_BKGD),   d alpha = T D
+//         d_dist_s += d alpha . e . softplus(raw_3)        (the exponential's own derivative, as the tail kernel takes it)
+//         d_z_s    += Gd . w                               (the explicit z of depth_map, RUN:447)
+//     then with dist_s = (z_{s+1} - z_s) |d| (s < S - 1), dist_{S-1} = 1e1 |d| (RUN:427):
+//         d_z_s -= d_dist_s |d|,  d_z_{s+1} += d_dist_s |d|  (s < S - 1),    d|d| = sum_s d_dist_s dz_s,    d_rays_d = d|d| . d / |d|
+//     d_z_{s+1} of a chunk's last sample belongs to the chunk behind, which this wave has already walked: the first sample of every chunk is
+//     therefore held back (pend) and written one chunk later by the lane that owns d_dist of the sample in front of it.
+// Occupancy: 48 registers and 6 KB of LDS would allow eight workgroups per CU; the launch bound asks for four (16 waves per CU) - the kernel
+// is a touch-once stream of raw / at (24 bytes per (sample, latent)) whose loads are issued one latent ahead, and N / 4 workgroups of a
+// training batch (256 at N = 1024) do not fill more than one round of that anyway.
+__global__ __launch_bounds__(kThreads, 4)
+void comp_zgrad_kernel(const RayGradArgs A) {
+#pragma clang fp contract(fast)
+    __shared__ float carry[kWaves][kMaxK][3];              // per latent: (g, x, D) of the first sample of the chunk behind (comp_adjoint_D)
+    const int lane = lane_id_opaque(), wave = wave_id();
+    const int64_t ray = (int64_t)blockIdx.x * kWaves + wave;
+    if (ray >= A.N) return;                                // (no workgroup barrier below: a wave is on its own)
+    const int S = A.S, K = A.K;
+    const float* rr = A.rays + ray * 11;
+    const float d0 = rr[3], d1 = rr[4], d2 = rr[5];
+    const float dnorm = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+    const bool wb = (A.flags & CFNERF_F_WHITE_BKGD) != 0;
+    for (int k = lane; k < K; k += 64) { carry[wave][k][0] = 0.f; carry[wave][k][1] = 0.f; carry[wave][k][2] = 0.f; }
+    float* const dz_out = A.d_z + ray * (int64_t)S;
+    float dn_acc = 0.f;                                    // this lane's part of d loss / d |d|
+    float pend = 0.f;                                      // d_z of the first sample of the chunk behind, without its d_dist_{s-1} term
+    const int nch = (S + 63) / 64;
+    for (int ch = nch - 1; ch >= 0; --ch) {
+        const int s = ch * 64 + lane;
+        const bool valid = s < S;
+        const int64_t p = ray * (int64_t)S + (valid ? s : 0);
+        const int tile_s = __builtin_amdgcn_readfirstlane((int)(ray * nch + ch));
+        const __amdgpu_buffer_rsrc_t raw_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.raw + (size_t)tile_s * K * 256), 0, K * 1024, 0x00020000);
+        const __amdgpu_buffer_rsrc_t at_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.at + (size_t)tile_s * K * 128), 0, K * 512, 0x00020000);
+        const float zv = A.z[p];
+        const float dz = (s >= S - 1) ? 1e1f : A.z[p + 1] - zv;
+        float dd = 0.f, dzs = 0.f;                         // d loss / d dist_s, the explicit-z term of d loss / d z_s
+        struct KIn { f32x4 rv; f32x2 at; float G0, G1, G2, Gd; };
+        auto fetch = [&](int k) {
+            KIn q;
+            q.rv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(raw_rs, lane * 16, k * 1024, /*nt*/ 2));
+            q.at = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(at_rs, lane * 8, k * 512, /*nt*/ 2));
+            q.G0 = A.d_rgb[ray * 3 * (int64_t)K + 0 * K + k]; q.G1 = A.d_rgb[ray * 3 * (int64_t)K + 1 * K + k];
+            q.G2 = A.d_rgb[ray * 3 * (int64_t)K + 2 * K + k];
+            q.Gd = (A.d_depth != nullptr) ? A.d_depth[ray * (int64_t)K + k] : 0.f;
+            return q;
+        };
+        KIn nx = fetch(0);
+        for (int k = 0; k < K; ++k) {
+            const KIn cur = nx;
+            if (k + 1 < K) nx = fetch(k + 1);
+            const f32x4 rv = cur.rv;
+            const float ea = cur.at[0], Tt = cur.at[1];
+            const float alpha = 1.f - ea;
+            const float c0 = t_sigmoid(rv[0]), c1 = t_sigmoid(rv[1]), c2 = t_sigmoid(rv[2]);
+            float g = (cur.G0 * c0 + cur.G1 * c1 + cur.G2 * c2) + cur.Gd * zv;      // d loss / d w_s
+            if (wb) g -= (cur.G0 + cur.G1 + cur.G2);                               // rgb_map += 1 - acc  (RUN:452)
+            const float xk = (1.f - alpha) + 1e-10f;                               // cumprod factor of RUN:443
+            float cg = carry[wave][k][0], cx = carry[wave][k][1], cD = carry[wave][k][2];
+            const float Dv = comp_adjoint_D(valid ? g : 0.f, xk, cg, cx, cD);
+            if (lane == 0) { carry[wave][k][0] = cg; carry[wave][k][1] = cx; carry[wave][k][2] = cD; }
+            if (valid) {
+                dd += (Tt * Dv) * ea * softplus_f(rv[3]);
+                dzs += cur.Gd * (alpha * Tt);
+            }
+        }
+        dn_acc += dd * dz;
+        const float flow = (valid && s < S - 1) ? dd * dnorm : 0.f;                // what d_dist_s moves from z_s to z_{s+1}
+        const float mine = dzs - flow + wave_prev_dpp(flow, 0.f);
+        if (valid && (lane != 0 || ch == 0)) dz_out[s] = mine;
+        if (lane == 63 && ch + 1 < nch) dz_out[s + 1] = pend + flow;               // (a chunk in front of another is full: s + 1 < S)
+        pend = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mine)));
+    }
+    const float dn = wave_sum(dn_acc);
+    if (lane < 11) {
+        float v = 0.f;
+        if (lane >= 3 && lane < 6) v = dn * (rr[lane] / dnorm);
+        A.d_rays[ray * 11 + lane] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// (b) One workgroup per ray walks its chunks front to back.  Per chunk the MFMA stage of input_grad_kernel leaves
+//         dgp [64, ic] = g_h[0] . W_pts0 + g_h[skip + 1] . W_skip[:, :ic],    dgd [64, icv] = g_v . W_views0[:, W:W+icv]
+//     in LDS (as d_x [P, ic + icv] it would be 47 MB in the caller's buffer at 1024 x 128 points, and a second pass over it).  The epilogue is the
+//     embedder's adjoint from the STASHED encoding - no transcendental (Embedder's backward, api.py):
+//         d_p[c] = dg[c] + sum_l 2^l (dg[3 + 6l + c] enc[6 + 6l + c] - dg[6 + 6l + c] enc[3 + 6l + c])
+//     (wave c = component c, lane = sample) and the adjoint of pts = o + d z:  d_o = sum_s d_p_s,  d_d += sum_s z_s d_p_s,  d_z_s += d_p_s . d;
+//     the view direction is the ray's: d_viewdirs is the same adjoint of sum_s dgd_s (wave 3) against gamma(d) of the ray's first point.
+// Occupancy: the MFMA stage's - three workgroups per CU (its registers, 3 x 41 KB of LDS; cfnerf_inputgrad.hip), grid = min(N, 3 n_cu).
+// N < 3 n_cu with a large S under-fills the chip: accepted, the walk of a ray stays in one workgroup so that nothing is added atomically.
+template <int W>
+__global__ __launch_bounds__(kThreads, 3)
+void ray_grad_kernel(const RayGradArgs A) {
+    __shared__ __attribute__((aligned(16))) float As[kTileM * kIgLdA];
+    __shared__ __attribute__((aligned(16))) float Bs[kIgKs * kIgLdB];
+    __shared__ __attribute__((aligned(16))) float Xs[kTileM * kIgMaxX];
+    __shared__ float Dp[kTileM][4];                        // d_p of the chunk's samples
+    __shared__ float Vs[32];                               // sum over the ray's samples of dgd
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+    const InputGradArgs& G = A.ig;
+    const int ic = G.ic, icv = G.icv, xs = ic + icv;
+    const int S = A.S, nch = (S + kTileM - 1) / kTileM;
+    const int Lp = (ic - 3) / 6, Lv = (icv - 3) / 6;
+
+    for (int64_t ray = blockIdx.x; ray < A.N; ray += gridDim.x) {
+        const float* rr = A.rays + ray * 11;
+        const float d0 = rr[3], d1 = rr[4], d2 = rr[5];
+        float acc_o = 0.f, acc_d = 0.f;                    // waves 0..2: this lane's sum of d_p[c], z d_p[c] over the chunks
+        float acc_v = 0.f;                                 // wave 3, lane j < icv: sum of dgd[:, j]
+        for (int ch = 0; ch < nch; ++ch) {
+            const int64_t p0 = ray * (int64_t)S + (int64_t)ch * kTileM;
+            const int rows_valid = min(kTileM, S - ch * kTileM);
+            ig_tile_mma<W>(G, p0, rows_valid, As, Bs, Xs);
+            const bool valid = lane < rows_valid;
+            if (wave < 3) {
+                float dp = 0.f;
+                if (valid) {
+                    const float* x = Xs + lane * xs;
+                    const float* e = A.enc + (p0 + lane) * 64;
+                    dp = x[wave];
+                    float f = 1.f;
+                    for (int l = 0; l < Lp; ++l, f *= 2.f) {
+                        const int cs = 3 + 6 * l + wave, cc = cs + 3;
+                        dp += f * (x[cs] * e[cc] - x[cc] * e[cs]);
+                    }
+                    acc_o += dp;
+                    acc_d += A.z[p0 + lane] * dp;
+                }
+                Dp[lane][wave] = dp;
+            } else if (lane < icv) {
+                float v = 0.f;
+                for (int r = 0; r < rows_valid; ++r) v += Xs[r * xs + ic + lane];
+                acc_v += v;
+            }
+            __syncthreads();
+            if (wave == 3 && valid) {
+                float* dst = A.d_z + p0 + lane;
+                *dst += (Dp[lane][0] * d0 + Dp[lane][1] * d1) + Dp[lane][2] * d2;
+            }
+            // (Dp is written again behind the barriers of the next chunk's slices)
+        }
+        if (wave == 3 && lane < 32) Vs[lane] = (lane < icv) ? acc_v : 0.f;
+        __syncthreads();
+        if (wave < 3) {
+            const float so = wave_sum(acc_o), sd = wave_sum(acc_d);
+            if (lane == 0) {
+                float* out = A.d_rays + ray * 11;
+                const float* gd = A.gd + ray * (int64_t)S * 32;
+                float dv = Vs[wave];
+                float f = 1.f;
+                for (int l = 0; l < Lv; ++l, f *= 2.f) {
+                    const int cs = 3 + 6 * l + wave, cc = cs + 3;
+                    dv += f * (Vs[cs] * gd[cc] - Vs[cc] * gd[cs]);
+                }
+                out[wave] = so;
+                out[3 + wave] += sd;
+                out[8 + wave] = dv;
+            }
+        }
+        __syncthreads();                                   // (Vs is free again)
+    }
+}
+
+static const void* ray_grad_fn(int W) {
+    switch (W) {
+#define CFN_W_CASE(w) case w: return reinterpret_cast<const void*>(ray_grad_kernel<w>);
+        CFN_FOR_EACH_WIDTH(CFN_W_CASE)
+#undef CFN_W_CASE
+    }
+    return nullptr;
+}
+
+hipError_t launch_comp_zgrad(const RayGradArgs& a, hipStream_t st) {
+    if (a.K > kMaxK) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(comp_zgrad_kernel, dim3((unsigned)((a.N + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_grad(const RayGradArgs& a, int W, int n_cu, hipStream_t st) {
+    const void* fn = ray_grad_fn(W);
+    if (!fn) return hipErrorInvalidValue;
+    if (a.ig.ic + a.ig.icv > kIgMaxX || a.ig.icv > 32 || a.ig.ic > 64) return hipErrorInvalidValue;
+    const int grid = (int)std::min<int64_t>(a.N, (int64_t)n_cu * 3);
+    void* args[] = {const_cast<RayGradArgs*>(&a)};
+    return hipLaunchKernel(fn, dim3(grid), dim3(kThreads), args, 0, st);
+}
+
+}  // namespace cfnerf

@@ -102,13 +102,23 @@ class Trainer:
 
     ``depth_lambda > 0``: ``step`` / ``forward_backward`` accept ``depth_rays=`` / ``target_depth=`` (data.DepthRayPool feeds them) and
     add the reference's depth-supervision term (module docstring; forward_backward has the entropy rule).  Without depth rays a step is
-    the plain step whatever ``depth_lambda`` is."""
+    the plain step whatever ``depth_lambda`` is.
+
+    ``ray_grad=True`` (one rank): ``forward_backward`` / ``step`` also leave ``self.d_rays [N,11]`` = d loss / d (the packed rays) and
+    ``self.d_z [N,S]`` = d loss / d z_vals of the step's WHOLE loss (means over the full batch), rows in launch order - colour rays, then
+    depth rays (CFNERF_F_RAY_GRAD; columns 6, 7 of ``d_rays`` - near / far - are zero, cfnerf.h).  ``api.pack_rays(...).backward(trainer.d_rays)``
+    chains them into a pose.  The default changes nothing: same buffers, same launches."""
 
     def __init__(self, net, lrate=5e-4, lrate_decay=250, beta1=0.0, world_size=1, group=None, start=0, force_allreduce=False,
                  overlap_comm=False, time_comm=False, max_rays_per_launch=None, latent_draws="launch", netchunk=1024 * 64, chunk=1024 * 32,
-                 depth_lambda=0.0):
+                 depth_lambda=0.0, ray_grad=False):
         if latent_draws not in LT.LATENT_DRAWS:
             raise ValueError(f"latent_draws must be one of {LT.LATENT_DRAWS}, got {latent_draws!r}")
+        if ray_grad and (int(world_size) > 1 or force_allreduce):
+            raise NotImplementedError("Trainer(ray_grad=True) with world_size > 1 / force_allreduce: the ray blocks of CFNERF_F_RAY_GRAD lie behind "
+                                      "the parameter gradient in the buffer whose tail the gradient exchange uses for the next step's latents")
+        self.ray_grad = bool(ray_grad)
+        self.d_rays = self.d_z = None
         self.latent_draws, self.netchunk, self.chunk = latent_draws, int(netchunk), (int(chunk) if chunk else None)
         # max_rays_per_launch: a step's shard larger than this is walked in EQUAL slices (forward -> loss -> backward per slice, the
         # gradient accumulated by cfnerf_render_bwd_accumulate, ONE exchange and ONE Adam step at the end): the train-step workspace
@@ -291,8 +301,20 @@ class Trainer:
                 first = min(self.netchunk // S, LT.ray_cuts(N, self.chunk)[0][1])
         return depth_rays, target_depth, first
 
+    def _ray_grad_buffers(self, N, S, n_max):
+        """``d_rays`` / ``d_z`` of a step of N rays, and the gradient buffer grown to hold the ray blocks of its largest pass (``n_max``
+        rays) behind the parameter gradient (cfnerf.h, CFNERF_F_RAY_GRAD)"""
+        dev = self.net.flat.device
+        if self.d_rays is None or tuple(self.d_z.shape) != (N, S):
+            self.d_rays, self.d_z = torch.zeros(N, 11, device=dev), torch.zeros(N, S, device=dev)
+        need = L.ray_grad_offsets(self.net.n_params, n_max, S)[2]
+        if self.gbuf.numel() < need:
+            self.gbuf = torch.zeros(need, device=dev)
+            self.grad = self.gbuf[:self.net.n_params]
+            self._xplan = None
+
     def _pass(self, a, b, t_vals, t_rand, eps, S, flags, target, beta, scalars, entropy, d_ent, grad=None, accumulate=False, z_vals=None,
-              weights=None, depth=None):
+              weights=None, depth=None, ray_grad=False):
         """One pass over rows [a, b) of the packed rays into the persistent buffers: the fused forward (``t_rand`` / ``z_vals`` and the
         optional ``weights [N,S,K]`` output are per-ray too and sliced alike) and, given a ``grad`` buffer, a STASH forward followed by the
         KDE-NLL loss (+ ``beta`` * entropy; means over the step's whole shard) into ``scalars`` and the backward into ``grad``
@@ -304,7 +326,8 @@ class Trainer:
         if LT.check_rows(eps, self.packed.shape[0], "rays of the shard"):         # CFNERF_F_EPS_ROWS: the slice's rows
             eps, flags = eps[a:b], flags | L.F_EPS_ROWS
         L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed[a:b]), L.ptr(t_vals), L.ptr(rows(t_rand)), L.ptr(rows(z_vals)), L.ptr(eps),
-                                      n, S, K, flags | (L.F_STASH if grad is not None else 0), L.ptr(self.rgb_map[a:b]), L.ptr(self.disp[a:b]),
+                                      n, S, K, flags | (L.F_STASH if grad is not None else 0) | (L.F_RAY_GRAD if ray_grad else 0),
+                                      L.ptr(self.rgb_map[a:b]), L.ptr(self.disp[a:b]),
                                       L.ptr(self.depth[a:b]), None, L.ptr(rows(weights)), None, None, L.ptr(entropy), st), "cfnerf_render_fwd")
         if grad is None:
             return
@@ -334,6 +357,10 @@ class Trainer:
         bwd = lib.cfnerf_render_bwd_accumulate if accumulate else lib.cfnerf_render_bwd
         L.check(bwd(net.handle, gen, L.ptr(self.d_rgb[a:b]), L.ptr(d_depth), L.ptr(d_ent) if self.beta1 and d_ent is not None else None,
                     L.ptr(grad), st), "cfnerf_render_bwd_accumulate" if accumulate else "cfnerf_render_bwd")
+        if ray_grad:                            # the pass's ray blocks (per-launch quantities: the next pass overwrites them) -> the step's rows
+            r_off, z_off, _ = L.ray_grad_offsets(net.n_params, n, S)
+            self.d_rays[a:b] = self.gbuf[r_off:r_off + n * 11].view(n, 11)
+            self.d_z[a:b] = self.gbuf[z_off:z_off + n * S].view(n, S)
 
     def forward_backward(self, H, W, focal, rays, target, t_rand=None, eps=None, near=0., far=1., ndc=True,
                          lindisp=False, white_bkgd=False, perturb=1., t_vals=None, eps_chunks=None, depth_rays=None, target_depth=None,
@@ -384,6 +411,8 @@ class Trainer:
         # the shard in n_sl equal slices: every loss term is taken with n_total = the FULL batch and beta1 / (world n_sl) on the slice's
         # entropy (equal slices: the mean of the slice means is the batch mean), so the slice gradients and the scalar contributions ADD.
         # One slice writes its scalars and entropy straight into the step's own buffers.
+        if self.ray_grad:
+            self._ray_grad_buffers(N, S, max(first, N - first) if first is not None else N // n_sl)
         if first is not None:
             return self._first_call_and_rest(first, N, t_vals, t_rand, eps, S, flags, target, depth)
         Ns = N // n_sl
@@ -399,7 +428,7 @@ class Trainer:
             sc_sum, ent_sum = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         for i in range(n_sl):
             self._pass(i * Ns, (i + 1) * Ns, t_vals, t_rand, eps, S, flags, target, self.beta1 / (self.world * n_sl), sc, ent, d_ent,
-                       grad=self.grad, accumulate=i > 0, depth=depth)
+                       grad=self.grad, accumulate=i > 0, depth=depth, ray_grad=self.ray_grad)
             if n_sl > 1:
                 sc_sum += sc
                 ent_sum += ent
@@ -417,8 +446,9 @@ class Trainer:
         self.net.ensure_workspace(max(first, N - first), S, self.net.K_samples)
         sc, ent = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         self._pass(0, first, t_vals, t_rand, eps, S, flags, target, self.beta1, self.scalars, self.entropy, self.d_ent, grad=self.grad,
-                   depth=depth)
-        self._pass(first, N, t_vals, t_rand, eps, S, flags, target, 0.0, sc, ent, None, grad=self.grad, accumulate=True, depth=depth)
+                   depth=depth, ray_grad=self.ray_grad)
+        self._pass(first, N, t_vals, t_rand, eps, S, flags, target, 0.0, sc, ent, None, grad=self.grad, accumulate=True, depth=depth,
+                   ray_grad=self.ray_grad)
         sc[:3] += self.scalars[:3]
         self.scalars[:3] = sc[:3]
         self.scalars[3] = -10.0 * torch.log10(sc[2])                        # HLP:16 on the batch's mse

@@ -102,7 +102,7 @@ enum {
                                            those entry points.  What is written equals, bit for bit, the same quantity of the launch without
                                            the flag.  Every other entry point that takes flags refuses it.  Without the flag every buffer
                                            shape and every output bit is what it was */
-    CFNERF_F_INPUT_GRAD = 0x80          /* (= 1 << 7, bit 7) the matching cfnerf_network_bwd also writes d loss / d x, the gradient with respect to the
+    CFNERF_F_INPUT_GRAD = 0x80,         /* (= 1 << 7, bit 7) the matching cfnerf_network_bwd also writes d loss / d x, the gradient with respect to the
                                            pre-embedded inputs (the reference's NeRF_Flows.forward is an autograd graph in x too: a learnable
                                            front end - pose correction, deformation field, learned encoding - trains through it).  Accepted by
                                            cfnerf_network_fwd only, and only together with CFNERF_F_STASH (the stash remembers it); refused with
@@ -113,6 +113,28 @@ enum {
                                            [P, input_ch + input_ch_views] row-major from x_off; the floats in between are not written.
                                            Every other entry point that takes flags refuses it.  Without the flag there is no extra launch and
                                            every buffer shape and every output bit is what it was */
+    CFNERF_F_RAY_GRAD   = 0x100         /* (= 1 << 8, bit 8) the matching cfnerf_render_bwd / cfnerf_render_bwd_accumulate also writes d loss / d rays and d loss / d z_vals
+                                           (the reference's render() is one autograd graph from c2w / rays_o / rays_d to the loss: pose
+                                           refinement, registration of an image against a trained model, a learnable warp on the rays).
+                                           Accepted by cfnerf_render_fwd only, and only together with CFNERF_F_STASH (the stash remembers it);
+                                           combines with CFNERF_F_EPS_ROWS, CFNERF_F_LINDISP, CFNERF_F_WHITE_BKGD, z_vals_opt and both precision
+                                           modes; refused with CFNERF_F_GEOMETRY / CFNERF_F_KSTATS_EXT.  The forward launch and every output bit
+                                           are what they are without the flag.  The backward of such a stash treats grad_flat as
+                                           [z_off + N * S] floats with
+                                               r_off = (cfnerf_param_count(cfg) + 63) / 64 * 64,   z_off = r_off + (N * 11 + 63) / 64 * 64 :
+                                           [0, param_count) the parameter gradient, bit for bit what it is without the flag (_accumulate
+                                           still ADDS there); d_rays [N,11] row-major from r_off; d_z [N,S] from z_off; the pad floats
+                                           between the blocks are not written.  Columns of d_rays: 0..2 d loss / d rays_o, 3..5 d loss /
+                                           d rays_d (through the sample points AND through |rays_d| of the composite's distances, RUN:429),
+                                           6, 7 written as 0 - the gradient for near / far is NOT computed: a caller who wants it chains
+                                           d_z through the sampling lines (RUN:510-532) on the host - 8..10 d loss / d viewdirs.  d_z is the
+                                           total gradient with respect to the sample depths (z_vals_opt if given, else the sampled z_vals):
+                                           the composite's distances and depth_map, and the sample points.  The two ray blocks are per-launch
+                                           quantities: ALWAYS overwritten, also by cfnerf_render_bwd_accumulate.  The cotangent of disp_map
+                                           stays ignored, as cfnerf_render_bwd ignores it for the parameters.  Exact-fp32 MFMA in both precision
+                                           modes, no atomics: bit-reproducible.  cfnerf_workspace_bytes does not change.  Every other entry
+                                           point that takes flags refuses it.  Without the flag there is no extra launch and every buffer
+                                           shape and every output bit is what it was */
 };
 
 CFNERF_API int         cfnerf_version(void);
@@ -263,7 +285,9 @@ CFNERF_API uint64_t cfnerf_model_stash_generation(const cfnerf_model* m);
  * has replaced that stash the call fails (CFNERF_E_INVALID) instead of differentiating the wrong batch.
  * d_depth_map may be NULL.  d_entropy points to ONE device float, d(loss)/d(loss_entropy) (e.g. beta1); NULL
  * means 0.  grad_flat [param_count] is OVERWRITTEN with the gradient in the flat parameter layout.  A CFNERF_F_EPS_ROWS
- * forward is differentiated with its per-ray rows, read from the caller's eps buffer (see CFNERF_F_EPS_ROWS).  */
+ * forward is differentiated with its per-ray rows, read from the caller's eps buffer (see CFNERF_F_EPS_ROWS).  There is no cotangent
+ * argument for disp_map: it is taken as zero.  If the forward carried CFNERF_F_RAY_GRAD, grad_flat is [z_off + N * S] floats and the call also
+ * writes d_rays [N,11] from r_off and d_z [N,S] from z_off (layout and columns at CFNERF_F_RAY_GRAD); without it only [0, param_count) is touched. */
 CFNERF_API int cfnerf_render_bwd(cfnerf_model* m, uint64_t stash_generation, const float* d_rgb_map, const float* d_depth_map,
                       const float* d_entropy, float* grad_flat, cfnerf_stream s);
 /* replaces: the same loss.backward() when ONE optimiser step's batch is walked in slices (the reference renders any N_rand and any
