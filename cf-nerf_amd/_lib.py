@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("CFNERF_LIB") or os.path.join(HERE, "libcfnerf_hip.so"
 F_TRAIN, F_LINDISP, F_WHITE_BKGD, F_STASH, F_EPS_ROWS, F_KSTATS_EXT, F_GEOMETRY, F_INPUT_GRAD = 1, 2, 4, 8, 16, 32, 64, 128
 F_RAY_GRAD = 256
 F_COTANGENTS = 512
+F_SEAM_GRAD = 1024          # goes into the white_bkgd argument of cfnerf_composite_bwd, not into a flags argument
 
 
 def input_grad_offset(n_params: int) -> int:
@@ -46,6 +47,23 @@ def cotangents(d_rgb_map, d_disp_map=None, d_weights=None, d_raw=None):
 def cotangents_arg(cot):
     """what goes into the d_rgb_map argument of cfnerf_render_bwd / _accumulate for a CFNERF_F_COTANGENTS stash: the struct's host address"""
     return C.cast(C.pointer(cot), C.c_void_p)
+
+
+class CompositeGrads(C.Structure):
+    """cfnerf_composite_grads of include/cfnerf.h: the host struct of device pointers that a CFNERF_F_SEAM_GRAD cfnerf_composite_bwd takes in
+    place of d_raw (``composite_grads_arg``), naming what it writes"""
+    _fields_ = [("d_raw", C.c_void_p), ("d_z_vals", C.c_void_p), ("d_rays_d", C.c_void_p)]
+
+
+def composite_grads(d_raw=None, d_z_vals=None, d_rays_d=None):
+    """A CompositeGrads of contiguous fp32 device tensors to write into (None -> NULL: not wanted)"""
+    val = lambda t: None if t is None else ptr(t).value
+    return CompositeGrads(val(d_raw), val(d_z_vals), val(d_rays_d))
+
+
+def composite_grads_arg(out):
+    """what goes into the d_raw argument of cfnerf_composite_bwd when F_SEAM_GRAD is or-ed into white_bkgd: the struct's host address"""
+    return C.cast(C.pointer(out), C.c_void_p)
 
 
 _P = C.c_void_p

@@ -232,6 +232,59 @@ def _wants_grad(*ts):
     return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
 
 
+def sample_points_reference(ray_batch, t_vals, t_rand=None, lindisp=False):
+    """RUN:510-534 in plain torch, in the dtype and on the device of ``ray_batch [N,11]``: near / far -> ``z_vals [N,S]`` (both ``lindisp``
+    forms, the jitter lines when ``t_rand [N,S]`` is given) and ``pts [N,S,3] = o + d z``.  The closed form the unfused seam's sampling node
+    differentiates (and what the CPU tests hold to the oracle); returns ``(z_vals, pts)``."""
+    rays_o, rays_d = ray_batch[:, 0:3], ray_batch[:, 3:6]
+    near, far = ray_batch[:, 6:7], ray_batch[:, 7:8]
+    t = t_vals.to(ray_batch)
+    if not lindisp:
+        z_vals = near * (1. - t) + far * t                                                                   # RUN:512
+    else:
+        z_vals = 1. / (1. / near * (1. - t) + 1. / far * t)                                                  # RUN:514
+    z_vals = z_vals.expand([ray_batch.shape[0], t.shape[0]])                                                 # RUN:516
+    if t_rand is not None:
+        mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])                                                     # RUN:520
+        upper = torch.cat([mids, z_vals[..., -1:]], -1)
+        lower = torch.cat([z_vals[..., :1], mids], -1)
+        z_vals = lower + (upper - lower) * t_rand.to(ray_batch)                                              # RUN:532
+    pts = rays_o[..., None, :] + rays_d[..., None, :] * z_vals[..., :, None]                                 # RUN:534
+    return z_vals, pts
+
+
+def _sample_points(rays, t_vals, t_rand, lindisp):
+    """cfnerf_sample_points of the packed fp32 ``rays [N,11]`` into new ``z_vals [N,S], pts [N,S,3]`` (RUN:510-534)"""
+    N, S = rays.shape[0], t_vals.shape[0]
+    z_vals = torch.empty(N, S, device=rays.device)
+    pts = torch.empty(N, S, 3, device=rays.device)
+    L.check(L.lib().cfnerf_sample_points(L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), L.F_LINDISP if lindisp else 0, N, S, L.ptr(z_vals),
+                                         L.ptr(pts), L.stream()), "cfnerf_sample_points")
+    return z_vals, pts
+
+
+class _SamplePointsFn(torch.autograd.Function):
+    """The unfused seam's sampling as an autograd node: the forward is the cfnerf_sample_points kernel (its unchanged bits), the backward
+    ``sample_points_reference`` differentiated by torch in fp32 on the device - N S 3 floats, elementwise.  ``(d_z, d_pts)`` reach all
+    eleven columns of ``d ray_batch``, near and far included (the view directions' three get zeros here: they are sliced off the rays)."""
+
+    @staticmethod
+    def forward(ctx, rays, t_vals, t_rand, lindisp):
+        ctx.lindisp = lindisp
+        ctx.t_rand = t_rand
+        ctx.save_for_backward(rays, t_vals)
+        return _sample_points(_f32c(rays), t_vals, t_rand, lindisp)
+
+    @staticmethod
+    def backward(ctx, d_z, d_pts):
+        rays, t_vals = ctx.saved_tensors
+        leaf = rays.detach().to(torch.float32).requires_grad_(True)
+        with torch.enable_grad():
+            z, pts = sample_points_reference(leaf, t_vals, ctx.t_rand, ctx.lindisp)
+        (g,) = torch.autograd.grad((z, pts), (leaf,), (d_z.to(z.dtype), d_pts.to(pts.dtype)))
+        return g.to(rays.dtype), None, None, None
+
+
 def get_rays(H, W, focal, c2w):
     """HLP:288-297 on the ray set-up kernel: ``rays_o, rays_d [H,W,3]`` on the GPU (of ``c2w`` if it lives on one, else the
     current device)."""
@@ -768,7 +821,8 @@ def _composite_fwd(raw, z_vals, rays_d, white_bkgd):
 
 class _CompositeFn(torch.autograd.Function):
     """raw2outputs (RUN:411-454) as an autograd node: cfnerf_composite_fwd + cfnerf_composite_bwd (stateless; differentiable with
-    respect to raw through every output: rgb_map, disp_map, weights, depth_map)."""
+    respect to raw, z_vals and rays_d through every output: rgb_map, disp_map, weights, depth_map).  The library is asked only for what
+    ``needs_input_grad`` asks: d_raw alone is the plain call; d_z_vals / d_rays_d are CFNERF_F_SEAM_GRAD, without d_raw for a detached raw."""
 
     @staticmethod
     def forward(ctx, raw, z_vals, rays_d, white_bkgd):
@@ -780,14 +834,25 @@ class _CompositeFn(torch.autograd.Function):
     def backward(ctx, d_rgb, d_disp, d_weights, d_depth):
         raw, z_vals, rays_d = ctx.saved_tensors
         N, S, K = raw.shape[0], raw.shape[1], raw.shape[2]
+        want_raw, want_z, want_d = ctx.needs_input_grad[:3]
         if N == 0 or (d_rgb is None and d_disp is None and d_weights is None and d_depth is None):
-            return torch.zeros_like(raw), None, None, None
-        d_raw = torch.empty_like(raw)
+            return (torch.zeros_like(raw) if want_raw else None, torch.zeros_like(z_vals) if want_z else None,
+                    torch.zeros_like(rays_d) if want_d else None, None)
+        d_raw = torch.empty_like(raw) if want_raw else None
         g_rgb = _f32c(d_rgb) if d_rgb is not None else torch.zeros(N, 3, K, device=raw.device)
         c = lambda t: _f32c(t) if t is not None else None
-        L.check(L.lib().cfnerf_composite_bwd(L.ptr(raw), L.ptr(z_vals), L.ptr(rays_d), N, S, K, ctx.white_bkgd, L.ptr(g_rgb), L.ptr(c(d_disp)),
-                                             L.ptr(c(d_depth)), L.ptr(c(d_weights)), L.ptr(d_raw), L.stream()), "cfnerf_composite_bwd")
-        return d_raw, None, None, None
+        g_disp, g_depth, g_weights = c(d_disp), c(d_depth), c(d_weights)         # (named: a converted copy must outlive the allocations below)
+        cots = (L.ptr(g_rgb), L.ptr(g_disp), L.ptr(g_depth), L.ptr(g_weights))
+        if not (want_z or want_d):
+            L.check(L.lib().cfnerf_composite_bwd(L.ptr(raw), L.ptr(z_vals), L.ptr(rays_d), N, S, K, ctx.white_bkgd, *cots, L.ptr(d_raw), L.stream()),
+                    "cfnerf_composite_bwd")
+            return d_raw, None, None, None
+        d_z = torch.empty_like(z_vals) if want_z else None
+        d_d = torch.empty_like(rays_d) if want_d else None
+        out = L.composite_grads(d_raw=d_raw, d_z_vals=d_z, d_rays_d=d_d)
+        L.check(L.lib().cfnerf_composite_bwd(L.ptr(raw), L.ptr(z_vals), L.ptr(rays_d), N, S, K, ctx.white_bkgd | L.F_SEAM_GRAD, *cots,
+                                             L.composite_grads_arg(out), L.stream()), "cfnerf_composite_bwd")
+        return d_raw, d_z, d_d, None
 
 
 class _DataParallelShim(nn.Module):
@@ -846,9 +911,9 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
     """RUN:411-454 on the standalone composite kernel.  ``raw_noise_std`` is accepted and has no effect,
     exactly like the reference (the noise is generated but never added, RUN:432-442)."""
     _need_gpu(raw, "raw")
-    if torch.is_grad_enabled() and raw.requires_grad:                # differentiable like the reference's (with respect to raw)
-        rc = raw.to(torch.float32).contiguous()
-        return _CompositeFn.apply(rc, _f32c(z_vals), _f32c(rays_d), bool(white_bkgd))
+    if _wants_grad(raw, z_vals, rays_d):                             # differentiable like the reference's: in raw, z_vals and rays_d
+        f = lambda t: t.to(torch.float32).contiguous() if t.requires_grad else _f32c(t)
+        return _CompositeFn.apply(f(raw), f(z_vals), f(rays_d), bool(white_bkgd))
     return _composite_fwd(_f32c(raw), _f32c(z_vals), _f32c(rays_d), white_bkgd)
 
 
@@ -983,7 +1048,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
     are accepted and never read, like the reference; ``N_importance > 0`` / ``network_fine`` - which the
     reference silently ignores (there is no fine pass) - are rejected.  ``retweights=True`` adds ``weights [N,S,K]``
     (the ``weights`` of raw2outputs, RUN:443).  Under autograd every returned map is on the graph, as in the reference: a loss on
-    ``disp_map``, ``raw`` or ``weights`` trains like one on ``rgb_map`` (CFNERF_F_COTANGENTS).
+    ``disp_map``, ``raw`` or ``weights`` trains like one on ``rgb_map`` (CFNERF_F_COTANGENTS).  With a
+    ``network_query_fn`` of the caller's the graph reaches ``ray_batch`` as well - all eleven columns, near / far included (section 13).
 
     A model in ``latent_draws = "netchunk"`` mode takes its train latents per netchunk (latents.py): ``chunk`` is then the
     ray cut of the reference's batchify_rays that the draw layout follows (``render`` passes its own; None = one cut).
@@ -1031,7 +1097,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
 
     fused = network_query_fn is None or getattr(network_query_fn, "_cfnerf_fused", False)
     if not fused:
-        return _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_rand, eps, is_train, lindisp, white_bkgd)
+        # the reference's graph runs from ray_batch to the loss whatever the query function is: rays that ask for a gradient stay on it
+        return _render_rays_unfused(ray_batch.to(torch.float32) if want_rays else rays, model, network_fn, network_query_fn, t_vals, t_rand, eps, is_train, lindisp, white_bkgd)
 
     if want_rays and fused and N > 0:
         # CFNERF_F_RAY_GRAD: gradients reach ray_batch (columns 6, 7 - near / far - get zeros) whether or not the network is frozen.  The eval
@@ -1109,13 +1176,15 @@ def _render_rays_hierarchical(ray_batch, network_fn, N_samples, N_importance, is
 
 
 def _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_rand, eps, is_train, lindisp, white_bkgd):
-    """A caller-supplied network_query_fn: sample with torch, query through it, composite kernel."""
+    """A caller-supplied network_query_fn: sample with the sampling kernel, query through it, composite kernel.  ``rays`` that ask for a
+    gradient (render_rays hands over the caller's ray_batch then) keep the reference's graph whole: z_vals and the points handed to the
+    query function are on it (_SamplePointsFn), rays_d and viewdirs are slices of it, raw2outputs differentiates in all three arguments."""
     rays_d, viewdirs = rays[:, 3:6], rays[:, 8:11]
-    N, S = rays.shape[0], t_vals.shape[0]
-    z_vals = torch.empty(N, S, device=rays.device)
-    pts0 = torch.empty(N, S, 3, device=rays.device)
-    L.check(L.lib().cfnerf_sample_points(L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), L.F_LINDISP if lindisp else 0, N, S, L.ptr(z_vals),
-                                         L.ptr(pts0), L.stream()), "cfnerf_sample_points")            # RUN:510-534
+    S = t_vals.shape[0]
+    if _wants_grad(rays):
+        z_vals, pts0 = _SamplePointsFn.apply(rays, t_vals, t_rand, bool(lindisp))                     # RUN:510-534
+    else:
+        z_vals, pts0 = _sample_points(rays, t_vals, t_rand, lindisp)                                  # RUN:510-534
     # NeRF_Flows.forward consumes it (a custom query fn honours the launch's latents too); the network sees points: one row per point
     model._next_eps = eps.repeat_interleave(S, 0) if eps.dim() == 3 else eps
     try:

@@ -154,7 +154,8 @@ static int check_device(const cfnerf_model* m) {
 // Flags that only some entry points implement: CFNERF_F_KSTATS_EXT widens the kstats / sqerr rows of the two render entry points,
 // CFNERF_F_GEOMETRY selects the geometry-only launch of the three fused-forward entry points, CFNERF_F_INPUT_GRAD asks the backward of
 // a cfnerf_network_fwd stash for d loss / d x, CFNERF_F_RAY_GRAD the backward of a cfnerf_render_fwd stash for d loss / d rays and d loss / d z_vals,
-// CFNERF_F_COTANGENTS makes the backward of a cfnerf_render_fwd stash read its d_rgb_map argument as a host cfnerf_cotangents.
+// CFNERF_F_COTANGENTS makes the backward of a cfnerf_render_fwd stash read its d_rgb_map argument as a host cfnerf_cotangents,
+// CFNERF_F_SEAM_GRAD belongs to the white_bkgd argument of cfnerf_composite_bwd alone.
 // Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
@@ -167,6 +168,8 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_RAY_GRAD (the ray gradient of cfnerf_render_fwd with CFNERF_F_STASH, written by cfnerf_render_bwd)", who);
     if (flags & CFNERF_F_COTANGENTS & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_COTANGENTS (the cotangent descriptor of cfnerf_render_fwd with CFNERF_F_STASH, read by cfnerf_render_bwd)", who);
+    if (flags & CFNERF_F_SEAM_GRAD)                     // (no entry point with a `flags` argument takes it)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_SEAM_GRAD (d_z_vals / d_rays_d of cfnerf_composite_bwd, passed in its white_bkgd argument)", who);
     return CFNERF_OK;
 }
 

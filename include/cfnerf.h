@@ -135,7 +135,7 @@ enum {
                                            in both precision modes, no atomics: bit-reproducible.  cfnerf_workspace_bytes does not change.  Every
                                            other entry point that takes flags refuses it.  Without the flag there is no extra launch and every
                                            buffer shape and every output bit is what it was */
-    CFNERF_F_COTANGENTS = 0x200         /* (= 1 << 9, bit 9) the matching cfnerf_render_bwd / cfnerf_render_bwd_accumulate takes cotangents for disp_map,
+    CFNERF_F_COTANGENTS = 0x200,        /* (= 1 << 9, bit 9) the matching cfnerf_render_bwd / cfnerf_render_bwd_accumulate takes cotangents for disp_map,
                                            weights and raw as well (in the reference every output of render() is on the autograd graph: a disparity
                                            loss, a density prior on raw[..., 3], a distortion or ray-entropy regulariser on the weights of
                                            raw2outputs, RUN:411-454).  There is no new entry point: with the flag in the stash, the `d_rgb_map` ARGUMENT
@@ -149,6 +149,17 @@ enum {
                                            optional members are NULL the backward launches exactly the kernels it launches without the flag: the
                                            parameter gradient, d_rays and d_z are the same bits.  cfnerf_workspace_bytes does not change.  Every other
                                            entry point that takes flags refuses it.  Without the flag every argument means what it meant */
+    CFNERF_F_SEAM_GRAD  = 0x400         /* (= 1 << 10, bit 10) cfnerf_composite_bwd also differentiates raw2outputs in z_vals and rays_d (RUN:424-429, 447:
+                                           in the reference raw2outputs(raw, z_vals, rays_d) is a graph in all three arguments - the link a script that
+                                           refines poses needs when it injects a network_query_fn of its own).  cfnerf_composite_bwd takes no flags:
+                                           the bit is passed in its `white_bkgd` ARGUMENT, and the background is white iff (white_bkgd & ~0x400) != 0,
+                                           so every value a caller passes today means what it meant.  There is no new entry point: with the bit, the
+                                           `d_raw` ARGUMENT is read as a pointer to a HOST struct cfnerf_composite_grads (below) - the caller passes
+                                           (float*)&grads - naming what to write: d_raw, d_z_vals, d_rays_d, each NULL when not wanted (all three NULL
+                                           is refused).  The struct is read during the call and not kept.  d_raw is written by the launch of the plain
+                                           call (the same bits); d_z_vals / d_rays_d by a second launch that reads raw once more, skipped when neither
+                                           is wanted, as the first is when d_raw is not.  No atomics: bit-reproducible.  Every entry point that takes
+                                           `flags` refuses the bit.  Without the bit the call is what it was */
 };
 
 /* The cotangents of a CFNERF_F_COTANGENTS backward: a HOST struct of DEVICE pointers, passed in place of d_rgb_map. */
@@ -158,6 +169,13 @@ typedef struct cfnerf_cotangents {
     const float* d_weights;             /* [N,S,K]   NULL = zeros; row-major, as weights_opt is written */
     const float* d_raw;                 /* [N,S,K,4] NULL = zeros; row-major, as raw_opt is written */
 } cfnerf_cotangents;
+
+/* What a CFNERF_F_SEAM_GRAD cfnerf_composite_bwd writes: a HOST struct of DEVICE pointers, passed in place of d_raw. */
+typedef struct cfnerf_composite_grads {
+    float* d_raw;                       /* [N,S,K,4] or NULL: not wanted */
+    float* d_z_vals;                    /* [N,S]     or NULL */
+    float* d_rays_d;                    /* [N,3]     or NULL */
+} cfnerf_composite_grads;
 
 CFNERF_API int         cfnerf_version(void);
 CFNERF_API const char* cfnerf_last_error(void);
@@ -341,7 +359,10 @@ CFNERF_API int cfnerf_network_bwd(cfnerf_model* m, uint64_t stash_generation, co
                        float* grad_flat, cfnerf_stream s);
 /* replaces: loss.backward() through raw2outputs(raw, z_vals, rays_d) RUN:411-454, stateless: the forward is recomputed from
  * raw [N,S,K,4], z_vals [N,S], rays_d [N,3].  d_rgb_map [N,3,K]; d_disp_map [N,K], d_depth_map [N,K], d_weights [N,S,K] may
- * be NULL (= zeros).  Writes d_raw [N,S,K,4] = d loss / d raw.  S <= 4096.                                               */
+ * be NULL (= zeros).  Writes d_raw [N,S,K,4] = d loss / d raw.  S <= 4096.
+ * With CFNERF_F_SEAM_GRAD or-ed into white_bkgd, d_raw is (float*)&grads of a host struct cfnerf_composite_grads and the call writes
+ * whichever of d_raw [N,S,K,4], d_z_vals [N,S] = d loss / d z_vals and d_rays_d [N,3] = d loss / d rays_d it names (see the flag):
+ * the distances z_{s+1} - z_s and |rays_d| of RUN:426-429 and depth_map's explicit z (RUN:447); the last interval 1e1 is a constant. */
 CFNERF_API int cfnerf_composite_bwd(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K, int white_bkgd,
                          const float* d_rgb_map, const float* d_disp_map, const float* d_depth_map, const float* d_weights,
                          float* d_raw, cfnerf_stream s);
