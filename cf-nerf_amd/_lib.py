@@ -11,6 +11,7 @@ F_TRAIN, F_LINDISP, F_WHITE_BKGD, F_STASH, F_EPS_ROWS, F_KSTATS_EXT, F_GEOMETRY,
 F_RAY_GRAD = 256
 F_COTANGENTS = 512
 F_SEAM_GRAD = 1024          # goes into the white_bkgd argument of cfnerf_composite_bwd, not into a flags argument
+F_CULL = 0x800              # cfnerf_sample_points: pts is a Cull; cfnerf_composite_fwd: or-ed into white_bkgd, weights_opt is a SparseRaw
 
 
 def input_grad_offset(n_params: int) -> int:
@@ -64,6 +65,32 @@ def composite_grads(d_raw=None, d_z_vals=None, d_rays_d=None):
 def composite_grads_arg(out):
     """what goes into the d_raw argument of cfnerf_composite_bwd when F_SEAM_GRAD is or-ed into white_bkgd: the struct's host address"""
     return C.cast(C.pointer(out), C.c_void_p)
+
+
+class Cull(C.Structure):
+    """cfnerf_cull of include/cfnerf.h: the occupancy grid and the outputs of a CFNERF_F_CULL cfnerf_sample_points, passed in place of pts
+    (``struct_arg``)"""
+    _fields_ = [("occ_bits", C.c_void_p), ("lo", C.c_float * 3), ("scale", C.c_float * 3), ("res", C.c_int32 * 3), ("outside", C.c_int32),
+                ("slot", C.c_void_p), ("ray_start", C.c_void_p), ("pts_c", C.c_void_p), ("ray_of", C.c_void_p)]
+
+
+class SparseRaw(C.Structure):
+    """cfnerf_sparse_raw of include/cfnerf.h: where the rows of a CFNERF_F_CULL cfnerf_composite_fwd's raw belong, passed in place of
+    weights_opt (``struct_arg``)"""
+    _fields_ = [("slot", C.c_void_p), ("ray_start", C.c_void_p), ("weights_opt", C.c_void_p)]
+
+
+def struct_arg(st):
+    """the host address of a descriptor struct, as the pointer argument it replaces"""
+    return C.cast(C.pointer(st), C.c_void_p)
+
+
+def dptr(t):
+    """Device pointer of a contiguous tensor of any dtype (None -> NULL): the integer members of Cull / SparseRaw"""
+    if t is None:
+        return None
+    assert t.is_contiguous(), t.shape
+    return t.data_ptr() or None
 
 
 _P = C.c_void_p

@@ -1198,6 +1198,102 @@ def _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_ra
     return ret
 
 
+# --------------------------------------------------------------------------------------------
+# Rendering through an occupancy grid (CFNERF_F_CULL): an opt-in EVALUATION path over the unfused seam.  Samples in empty cells never
+# reach the network; the composite takes raw rows for the kept samples only.  Inference only; one synchronising device-to-host copy per
+# call (the kept count) - the train step's "nothing synchronises" contract is about the train step and is not affected.
+@torch.no_grad()
+def cull_points(ray_batch, grid, t_vals=None, t_rand=None, lindisp=False, outside="keep"):
+    """cfnerf_sample_points with CFNERF_F_CULL on the packed ``ray_batch [N,11]`` and an ``evaluate.OccupancyGrid``: the sampling lines of
+    render_rays (RUN:510-534) + the keep / skip decision of every sample + the compact list of the kept points, in (ray, sample) order.
+    A sample is kept iff the cell ``floor((p - lo) * scale)`` of its point is occupied; ``outside`` = ``"keep"`` / ``"cull"`` decides for
+    points outside the box.  Returns ``z_vals [N,S]`` (the bits of the plain call), ``slot [N,S]`` int32 (row in the compact list, -1 =
+    culled), ``ray_start [N+1]`` int64, ``pts [P',3]``, ``ray_of [P']`` int32 and ``count`` = P' (read back from the device: this call
+    synchronises)."""
+    z_vals, slot, ray_start, pts_c, ray_of = _cull_launch(ray_batch, grid, t_vals, t_rand, lindisp, outside)
+    count = int(ray_start[-1].item())                                # the one device-to-host copy: it synchronises
+    return {'z_vals': z_vals, 'slot': slot, 'ray_start': ray_start, 'pts': pts_c[:count], 'ray_of': ray_of[:count], 'count': count}
+
+
+def _cull_launch(ray_batch, grid, t_vals=None, t_rand=None, lindisp=False, outside="keep"):
+    """the launches of ``cull_points`` without the copy of the kept count: ``(z_vals, slot, ray_start, pts_c [N*S,3], ray_of [N*S])``"""
+    _need_gpu(ray_batch, "ray_batch")
+    if outside not in ("keep", "cull"):
+        raise ValueError(f"outside must be 'keep' or 'cull', got {outside!r}")
+    rays = _f32c(ray_batch)
+    dev = rays.device
+    t_vals = t_vals_table(dev) if t_vals is None else t_vals.to(dev, torch.float32).contiguous()
+    t_rand = None if t_rand is None else _f32c(t_rand.to(dev))
+    N, S = rays.shape[0], t_vals.shape[0]
+    bits = grid.bits_on(dev)
+    z_vals = torch.empty(N, S, device=dev)
+    slot = torch.empty(N, S, dtype=torch.int32, device=dev)
+    ray_start = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    pts_c = torch.empty(N * S, 3, device=dev)
+    ray_of = torch.empty(N * S, dtype=torch.int32, device=dev)
+    if N == 0:                                                       # (empty batch: no buffer to describe, nothing to launch)
+        return z_vals, slot, ray_start.zero_(), pts_c, ray_of
+    f3 = lambda v: (C.c_float * 3)(*(float(x) for x in v))           # (fp32 values: exact through Python's float)
+    d = L.Cull(L.dptr(bits), f3(grid.lo), f3(grid.scale), (C.c_int32 * 3)(*(int(r) for r in grid.res)), int(outside == "cull"),
+               L.dptr(slot), L.dptr(ray_start), L.dptr(pts_c), L.dptr(ray_of))
+    L.check(L.lib().cfnerf_sample_points(L.ptr(rays), L.ptr(t_vals), L.ptr(t_rand), (L.F_LINDISP if lindisp else 0) | L.F_CULL, N, S,
+                                         L.ptr(z_vals), L.struct_arg(d), L.stream()), "cfnerf_sample_points")
+    return z_vals, slot, ray_start, pts_c, ray_of
+
+
+def raw2outputs_sparse(raw_c, slot, ray_start, z_vals, rays_d, white_bkgd=False, retweights=False):
+    """raw2outputs (RUN:411-454) on ``raw_c [P',K,4]``, the rows of the kept samples of ``cull_points`` alone: the tuple raw2outputs returns,
+    ``(rgb_map [N,3,K], disp_map [N,K], weights [N,S,K] or None without retweights, depth_map [N,K])`` - bit for bit what raw2outputs gives
+    on the dense raw in which every culled sample has the density latent -1e4.  Inference only."""
+    _need_gpu(raw_c, "raw_c")
+    if _wants_grad(raw_c):
+        raise RuntimeError("raw2outputs_sparse is inference only (the sparse composite has no backward): call it under torch.no_grad(), or "
+                           "scatter the rows into a dense raw and use raw2outputs for a differentiable composite")
+    raw_c, z_vals, rays_d = _f32c(raw_c), _f32c(z_vals), _f32c(rays_d)
+    N, S = z_vals.shape
+    if raw_c.dim() != 3 or raw_c.shape[2] != 4:
+        raise ValueError(f"raw_c must be [P',K,4], got {tuple(raw_c.shape)}")
+    if tuple(slot.shape) != (N, S) or slot.dtype != torch.int32 or tuple(ray_start.shape) != (N + 1,) or ray_start.dtype != torch.int64:
+        raise ValueError("slot must be int32 [N,S] and ray_start int64 [N+1], as cull_points returns them")
+    K, dev = raw_c.shape[1], z_vals.device
+    rgb_map = torch.empty(N, 3, K, device=dev)
+    disp_map = torch.empty(N, K, device=dev)
+    depth_map = torch.empty(N, K, device=dev)
+    weights = torch.empty(N, S, K, device=dev) if retweights else None
+    sp = L.SparseRaw(L.dptr(slot.contiguous()), L.dptr(ray_start.contiguous()), L.dptr(weights))
+    L.check(L.lib().cfnerf_composite_fwd(L.ptr(raw_c) if raw_c.numel() else None, L.ptr(z_vals), L.ptr(rays_d), N, S, K,
+                                         int(bool(white_bkgd)) | L.F_CULL, L.ptr(rgb_map), L.ptr(disp_map), L.ptr(depth_map), L.struct_arg(sp),
+                                         L.stream()), "cfnerf_composite_fwd")
+    return rgb_map, disp_map, weights, depth_map
+
+
+@torch.no_grad()
+def render_rays_culled(ray_batch, network_fn, grid, t_vals=None, lindisp=False, white_bkgd=False, retweights=False, outside="keep"):
+    """Eval render of ``ray_batch [N,11]`` through an ``evaluate.OccupancyGrid`` (eval branch, eval latents): ``cull_points`` -> cfnerf_embed
+    of the kept points -> the view-direction embedding gathered by ``ray_of`` -> ``NeRF_Flows.forward(x_c, is_test=True)`` on the P' kept
+    points -> ``raw2outputs_sparse``.  Returns ``{'rgb_map' [N,3,K], 'disp_map' [N,K], 'depth_map' [N,K], 'count': P'}`` (+ ``weights``).
+    With P' = 0 the network is not called: an empty ray is the background.  With an all-ones grid the result has the bits of the unfused
+    pipeline (sample, embed, forward, raw2outputs)."""
+    model = _unwrap(network_fn)
+    c = cull_points(ray_batch, grid, t_vals=t_vals, lindisp=lindisp, outside=outside)
+    rays = _f32c(ray_batch)
+    K, count = model.K_samples, c['count']
+    if count > 0:
+        ic, icv = model.input_ch, model.input_ch_views
+        x_c = torch.empty(count, ic + icv, device=rays.device)
+        x_c[:, :ic] = _embed_fwd(c['pts'], (ic - 3) // 6, ic)
+        x_c[:, ic:] = _embed_fwd(rays[:, 8:11].contiguous(), (icv - 3) // 6, icv)[c['ray_of'].long()]
+        raw_c = network_fn(x_c, False, True)[0]
+    else:
+        raw_c = torch.empty(0, K, 4, device=rays.device)
+    rgb_map, disp_map, weights, depth_map = raw2outputs_sparse(raw_c, c['slot'], c['ray_start'], c['z_vals'], rays[:, 3:6].contiguous(),
+                                                               white_bkgd=white_bkgd, retweights=retweights)
+    ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'depth_map': depth_map, 'count': count}
+    if retweights:
+        ret['weights'] = weights
+    return ret
+
+
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """RUN:88-100."""
     all_ret = {}

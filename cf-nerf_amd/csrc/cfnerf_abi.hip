@@ -155,7 +155,8 @@ static int check_device(const cfnerf_model* m) {
 // CFNERF_F_GEOMETRY selects the geometry-only launch of the three fused-forward entry points, CFNERF_F_INPUT_GRAD asks the backward of
 // a cfnerf_network_fwd stash for d loss / d x, CFNERF_F_RAY_GRAD the backward of a cfnerf_render_fwd stash for d loss / d rays and d loss / d z_vals,
 // CFNERF_F_COTANGENTS makes the backward of a cfnerf_render_fwd stash read its d_rgb_map argument as a host cfnerf_cotangents,
-// CFNERF_F_SEAM_GRAD belongs to the white_bkgd argument of cfnerf_composite_bwd alone.
+// CFNERF_F_SEAM_GRAD belongs to the white_bkgd argument of cfnerf_composite_bwd alone, CFNERF_F_CULL turns the pts argument of
+// cfnerf_sample_points into a host cfnerf_cull (and travels in the white_bkgd argument of cfnerf_composite_fwd).
 // Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
@@ -170,6 +171,20 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_COTANGENTS (the cotangent descriptor of cfnerf_render_fwd with CFNERF_F_STASH, read by cfnerf_render_bwd)", who);
     if (flags & CFNERF_F_SEAM_GRAD)                     // (no entry point with a `flags` argument takes it)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_SEAM_GRAD (d_z_vals / d_rays_d of cfnerf_composite_bwd, passed in its white_bkgd argument)", who);
+    if (flags & CFNERF_F_CULL & ~allowed)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_CULL (the occupancy-grid descriptor of cfnerf_sample_points; cfnerf_composite_fwd takes the bit in its white_bkgd argument)", who);
+    return CFNERF_OK;
+}
+
+// the host descriptor of a CFNERF_F_CULL cfnerf_sample_points, checked before anything touches a device
+static int check_cull(const cfnerf_cull* c) {
+    if (!c) return fail(CFNERF_E_INVALID, "CFNERF_F_CULL: the pts argument must be (float*)&cull of a host struct cfnerf_cull, got NULL");
+    static const char* const names[] = {"occ_bits", "slot", "ray_start", "pts_c", "ray_of"};
+    const void* const ptrs[] = {c->occ_bits, c->slot, c->ray_start, c->pts_c, c->ray_of};
+    for (int i = 0; i < 5; ++i)
+        if (!ptrs[i]) return fail(CFNERF_E_INVALID, "CFNERF_F_CULL: member %s of cfnerf_cull is NULL", names[i]);
+    for (int d = 0; d < 3; ++d)
+        if (c->res[d] < 1) return fail(CFNERF_E_INVALID, "CFNERF_F_CULL: member res[%d] of cfnerf_cull is %d (every axis needs at least 1 cell)", d, c->res[d]);
     return CFNERF_OK;
 }
 
@@ -295,7 +310,21 @@ int cfnerf_embed(const float* x, int64_t P, int multires, float* out, cfnerf_str
 
 int cfnerf_sample_points(const float* rays, const float* t_vals, const float* t_rand, int flags, int64_t N, int S, float* z_vals,
                          float* pts, cfnerf_stream s) {
-    if (int rc = refuse_mode_flags(flags, 0, "cfnerf_sample_points")) return rc;
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_CULL, "cfnerf_sample_points")) return rc;
+    if (flags & CFNERF_F_CULL) {                 // pts is a host cfnerf_cull: z_vals + the keep / skip decisions + the compact point list
+        const cfnerf_cull* c = reinterpret_cast<const cfnerf_cull*>(pts);
+        if (int rc = check_cull(c)) return rc;
+        if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
+        if (N * (int64_t)S > 0x7fffffff) return fail(CFNERF_E_UNSUPPORTED, "CFNERF_F_CULL: N * S must stay below 2^31 (slot holds 32-bit rows)");
+        if (N > 0 && (!rays || !t_vals || !z_vals)) return fail(CFNERF_E_INVALID, "NULL argument");
+        CullArgs a{};
+        a.rays = rays; a.t_vals = t_vals; a.t_rand = t_rand; a.occ_bits = c->occ_bits;
+        for (int d = 0; d < 3; ++d) { a.lo[d] = c->lo[d]; a.scale[d] = c->scale[d]; a.res[d] = c->res[d]; }
+        a.outside = c->outside != 0; a.lindisp = (flags & CFNERF_F_LINDISP) != 0; a.S = S; a.N = N;
+        a.z_vals = z_vals; a.slot = c->slot; a.ray_start = c->ray_start; a.pts_c = c->pts_c; a.ray_of = c->ray_of;
+        HIPCHK(launch_cull(a, (hipStream_t)s));  // (N == 0: ray_start[0] = 0)
+        return CFNERF_OK;
+    }
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
     if (N == 0) return CFNERF_OK;
     if (!rays || !t_vals || !z_vals) return fail(CFNERF_E_INVALID, "NULL argument");
@@ -438,6 +467,20 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
 int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K,
                          int white_bkgd, float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
                          cfnerf_stream s) {
+    if (white_bkgd & CFNERF_F_CULL) {            // raw is [P',K,4], weights_opt a host cfnerf_sparse_raw; white iff (white_bkgd & ~0x800) != 0
+        const cfnerf_sparse_raw* sp = reinterpret_cast<const cfnerf_sparse_raw*>(weights_opt);
+        if (!sp) return fail(CFNERF_E_INVALID, "CFNERF_F_CULL: the weights_opt argument must be (float*)&sp of a host struct cfnerf_sparse_raw, got NULL");
+        if (!sp->slot) return fail(CFNERF_E_INVALID, "CFNERF_F_CULL: member slot of cfnerf_sparse_raw is NULL");
+        if (!sp->ray_start) return fail(CFNERF_E_INVALID, "CFNERF_F_CULL: member ray_start of cfnerf_sparse_raw is NULL");
+        if (N < 0 || S < 1 || K < 1) return fail(CFNERF_E_INVALID, "bad N/S/K");
+        if (N == 0) return CFNERF_OK;
+        // (raw may be NULL: P' = 0 leaves nothing to read - every descriptor is then empty)
+        if (!z_vals || !rays_d || !rgb_map || !disp_map || !depth_map) return fail(CFNERF_E_INVALID, "NULL argument");
+        if ((int64_t)S * K * 16 >= (1ll << 31)) return fail(CFNERF_E_UNSUPPORTED, "cfnerf_composite_fwd: S * K * 16 bytes per ray must stay below 2 GiB");
+        HIPCHK(launch_composite_sparse(raw, sp->slot, sp->ray_start, z_vals, rays_d, N, S, K, (white_bkgd & ~CFNERF_F_CULL) != 0, rgb_map, disp_map,
+                                       depth_map, sp->weights_opt, (hipStream_t)s));
+        return CFNERF_OK;
+    }
     if (N < 0 || S < 1 || K < 1) return fail(CFNERF_E_INVALID, "bad N/S/K");
     if (N == 0) return CFNERF_OK;
     if (!raw || !z_vals || !rays_d || !rgb_map || !disp_map || !depth_map) return fail(CFNERF_E_INVALID, "NULL argument");

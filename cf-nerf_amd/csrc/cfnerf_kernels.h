@@ -70,6 +70,22 @@ hipError_t launch_sample_pdf(const float* rays, const float* t_vals, const float
 hipError_t launch_embed(const float* x, int64_t P, int multires, float* out, hipStream_t st);
 hipError_t launch_sample_points(const float* rays, const float* t_vals, const float* t_rand, int flags, int64_t N, int S, float* z, float* pts,
                                 hipStream_t st);
+// CFNERF_F_CULL (cfnerf_cull.hip): the sampling lines of cfnerf_sample_points + the occupancy test + the compaction, from a cfnerf_cull
+struct CullArgs {
+    const float *rays, *t_vals, *t_rand;
+    const uint32_t* occ_bits;
+    float lo[3], scale[3];
+    int32_t res[3], outside, lindisp, S;
+    int64_t N;
+    float* z_vals;            // [N,S]
+    int32_t* slot;            // [N,S]
+    int64_t* ray_start;       // [N+1]
+    float* pts_c;             // [N*S,3]
+    int32_t* ray_of;          // [N*S]
+};
+hipError_t launch_cull(const CullArgs& a, hipStream_t st);      // count, scan, emit
+hipError_t launch_composite_sparse(const float* raw_c, const int32_t* slot, const int64_t* ray_start, const float* z, const float* d, int64_t N,
+                                   int S, int K, int wb, float* rgb, float* disp, float* depth, float* weights, hipStream_t st);
 hipError_t launch_pack_index(const PackDesc* descs, int ndesc, uint32_t total, uint32_t* table /*[total][3]*/, hipStream_t st);      // once per model
 hipError_t launch_pack(const float* flat, float* packed, void* packed16, const uint32_t* table, uint32_t total, hipStream_t st);
 

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, render, t_vals_table
+from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, render, render_rays_culled, t_vals_table
 
 
 def render_path_train(render_poses, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0):
@@ -99,7 +99,7 @@ def kde_nll(rgb_map, gt):
 
 @torch.no_grad()
 def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, lindisp=False, white_bkgd=False,
-                       rows=None, want_maps=False, t_vals=None, gt=None, stats="basic", **_ignored):
+                       rows=None, want_maps=False, t_vals=None, gt=None, stats="basic", occupancy=None, **_ignored):
     """Eval render of rows ``rows=(r0, r1)`` (default: all) of the image seen from ``c2w`` with the reductions over the
     K latent samples fused into the kernel.  Returns a dict with ``rgb_mean [h,W,3]``, ``rgb_unc [h,W,3]``
     (= ``np.std(rgbs,-1) * n/(n-1)``, RUN:1129-1130), ``disp_mean [h,W]`` (RUN:1124), ``depth_mean [h,W]`` and, if
@@ -115,9 +115,18 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
 
     ``stats="geometry"`` (CFNERF_F_GEOMETRY: the launch skips the colour branch) returns ``depth_mean``, ``disp_mean``, ``depth_unc``,
     ``disp_unc``, ``acc_mean``, ``acc_unc [h,W]`` only - 24 B per pixel, each with the bits ``stats="ext"`` gives it; ``white_bkgd`` has no
-    effect on them, ``want_maps`` / ``gt`` are refused."""
+    effect on them, ``want_maps`` / ``gt`` are refused.
+
+    ``occupancy=`` an ``OccupancyGrid`` (``stats="basic"`` only) renders through the grid instead (CFNERF_F_CULL, ``api.render_rays_culled``):
+    samples in empty cells never reach the network.  The rays are walked in bounded chunks, each with one synchronising copy of its kept
+    count, and the keys above are derived in torch from the per-K maps of the sparse composite, with the same estimators."""
     if stats not in ("basic", "ext", "geometry"):
         raise ValueError(f"stats must be 'basic', 'ext' or 'geometry', got {stats!r}")
+    if occupancy is not None:
+        if stats != "basic":
+            raise ValueError(f"occupancy= supports stats='basic' only, got {stats!r}: the culled path ends in the standalone composite, which has "
+                             "no acc_map (the accumulated opacity of stats='ext' / 'geometry' exists in the fused kernels alone)")
+        return _render_uncertainty_culled(H, W, focal, c2w, network_fn, occupancy, near, far, ndc, lindisp, white_bkgd, rows, want_maps, t_vals, gt)
     if stats == "geometry":
         if want_maps or gt is not None:
             raise ValueError("stats='geometry' renders no colour: want_maps / gt are not arguments of it (api.render_geometry gives the per-K maps)")
@@ -187,6 +196,43 @@ def _render_uncertainty_geometry(H, W, focal, c2w, network_fn, near, far, ndc, l
     return {k: kst[:, i].reshape(h, W) for i, k in enumerate(keys)}
 
 
+_CULL_RAY_CHUNK = 1 << 14      # rays per cull / network / composite round of render_uncertainty(occupancy=): bounds x_c and raw_c (dense worst case)
+
+
+def k_stats(rgb_map, disp_map, depth_map):
+    """The evaluation loop's reductions over the K latent samples (RUN:1122-1131) of per-K maps ``rgb_map [...,3,K]``, ``disp_map`` /
+    ``depth_map [...,K]`` in torch: ``(rgb_mean, rgb_unc = np.std * n/(n-1), disp_mean, depth_mean)`` - what the fused kernels write as kstats."""
+    K = rgb_map.shape[-1]
+    return rgb_map.mean(-1), rgb_map.std(-1, unbiased=False) * K / (K - 1), disp_map.mean(-1), depth_map.mean(-1)
+
+
+def _render_uncertainty_culled(H, W, focal, c2w, network_fn, grid, near, far, ndc, lindisp, white_bkgd, rows, want_maps, t_vals, gt):
+    """``render_uncertainty(occupancy=grid)``: ``api.render_rays_culled`` on chunks of the rays, the K-statistics in torch (``k_stats``)."""
+    net = _unwrap(network_fn)
+    dev = net.device
+    K = net.K_samples
+    if K < 2:
+        raise ValueError("render_uncertainty needs K_samples >= 2 (std * n/(n-1))")
+    r0, r1 = rows if rows is not None else (0, H)
+    n, h = (r1 - r0) * W, r1 - r0
+    packed = _pack_rays(H, W, focal, c2w=c2w, n=n, pixel0=r0 * W, ndc=ndc, near=near, far=far, device=dev)
+    rgb_map, disp_map, depth_map = torch.empty(n, 3, K, device=dev), torch.empty(n, K, device=dev), torch.empty(n, K, device=dev)
+    kept = 0
+    for i in range(0, n, _CULL_RAY_CHUNK):
+        o = render_rays_culled(packed[i:i + _CULL_RAY_CHUNK], network_fn, grid, t_vals=t_vals, lindisp=lindisp, white_bkgd=white_bkgd)
+        rgb_map[i:i + _CULL_RAY_CHUNK], disp_map[i:i + _CULL_RAY_CHUNK], depth_map[i:i + _CULL_RAY_CHUNK] = o['rgb_map'], o['disp_map'], o['depth_map']
+        kept += o['count']
+    rgb_mean, rgb_unc, disp_mean, depth_mean = k_stats(rgb_map, disp_map, depth_map)
+    out = dict(rgb_mean=rgb_mean.reshape(h, W, 3), rgb_unc=rgb_unc.reshape(h, W, 3), disp_mean=disp_mean.reshape(h, W),
+               depth_mean=depth_mean.reshape(h, W), kept_samples=kept)
+    if want_maps:
+        out.update(rgb_map=rgb_map.reshape(h, W, 3, K), disp_map=disp_map.reshape(h, W, K), depth_map=depth_map.reshape(h, W, K))
+    if gt is not None:
+        sq = (rgb_mean - gt.to(dev, torch.float32).reshape(n, 3)) ** 2
+        out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
+    return out
+
+
 def sigma_stats(alpha):
     """Density statistics over the K latent samples (last axis) of the density latents ``alpha [...,K]``: sigma = softplus(alpha_k) (RUN:424),
     its mean and ``np.std * n/(n-1)`` (RUN:1130, the estimator of every other uncertainty map here).  Returns ``(sigma_mean, sigma_unc)``."""
@@ -240,6 +286,76 @@ def density_grid(network_fn, lo, hi, res, chunk=1 << 20, eps_alpha=None, return_
     if return_raw:
         out["alpha"] = alpha.reshape(X, Y, Z, K)
     return out
+
+
+class OccupancyGrid:
+    """A bit per cell of the axis-aligned box ``lo .. hi`` cut into ``res = (X, Y, Z)`` cells: what ``api.cull_points`` /
+    ``render_uncertainty(occupancy=)`` skip empty space with (CFNERF_F_CULL).  Cell ``(ix, iy, iz)`` is bit ``c & 31`` of word ``c >> 5`` of
+    ``bits`` (int32 words holding the 32-bit patterns), ``c = (ix * Y + iy) * Z + iz``; the cell of a point is ``floor((p - lo) * scale)`` per
+    axis with ``scale = res / (hi - lo)`` computed ONCE, here, in fp32 - the kernel uses this ``scale``, so host and device agree on every
+    cell face.  ``lo``, ``hi``, ``scale`` are numpy fp32 ``[3]``, ``res`` a tuple of ints, ``fraction`` the share of occupied cells."""
+
+    def __init__(self, bits, lo, hi, res, fraction):
+        self.bits = bits
+        self.lo, self.hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        self.res = tuple(int(r) for r in res)
+        if min(self.res) < 1 or not (self.hi > self.lo).all():
+            raise ValueError(f"an occupancy grid needs res >= 1 and hi > lo on every axis, got res={self.res} lo={self.lo} hi={self.hi}")
+        self.scale = np.asarray(self.res, np.float32) / (self.hi - self.lo)           # fp32 / fp32: the number the kernel multiplies by
+        self.fraction = float(fraction)
+        self._dev = {}
+
+    def bits_on(self, device):
+        """``bits`` on ``device`` (uploaded once per device)"""
+        device = torch.device(device)
+        if self.bits.device == device:
+            return self.bits
+        if device not in self._dev:
+            self._dev[device] = self.bits.to(device)
+        return self._dev[device]
+
+    @staticmethod
+    def pack_mask(mask):
+        """``mask [X,Y,Z]`` bool -> int32 words ``[ceil(XYZ / 32)]`` in the layout above (on the mask's device)"""
+        flat = mask.reshape(-1).to(torch.int64)
+        pad = (-flat.numel()) % 32
+        if pad:
+            flat = torch.cat([flat, flat.new_zeros(pad)])
+        w = (flat.reshape(-1, 32) << torch.arange(32, device=flat.device)).sum(1)                # in [0, 2^32)
+        return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)                         # the same 32 bits as a signed word
+
+    @staticmethod
+    def dilate_mask(mask, n):
+        """``mask [X,Y,Z]`` grown by ``n`` cells along each axis (a cell is set iff a cell within ``n`` steps on every axis is)"""
+        n = int(n)
+        if n <= 0:
+            return mask
+        m = torch.nn.functional.max_pool3d(mask[None, None].to(torch.float32), kernel_size=2 * n + 1, stride=1, padding=n)
+        return m[0, 0] > 0
+
+    @classmethod
+    def from_mask(cls, mask, lo, hi):
+        """The grid of a bool ``mask [X,Y,Z]`` (a CPU or a GPU tensor; ``bits`` stays on its device) on the box ``lo .. hi``"""
+        mask = torch.as_tensor(mask)
+        if mask.dim() != 3 or mask.dtype != torch.bool:
+            raise ValueError(f"mask must be a bool tensor [X,Y,Z], got {mask.dtype} {tuple(mask.shape)}")
+        return cls(cls.pack_mask(mask), lo, hi, mask.shape, mask.float().mean().item() if mask.numel() else 0.)
+
+    @classmethod
+    @torch.no_grad()
+    def from_network(cls, net, lo, hi, res, threshold, dilate=1, chunk=1 << 20, eps_alpha=None):
+        """The grid of a trained network: ``density_grid(..., return_raw=True)`` on the ``(X+1, Y+1, Z+1)`` lattice of cell corners; a cell
+        is occupied iff any of its 8 corners has ``softplus(max_k alpha) > threshold`` (the largest density over the K latents); the mask
+        is then grown by ``dilate`` cells along each axis, which covers surfaces that pass between corners."""
+        X, Y, Z = (int(r) for r in res)
+        alpha = density_grid(net, lo, hi, (X + 1, Y + 1, Z + 1), chunk=chunk, eps_alpha=eps_alpha, return_raw=True)["alpha"]
+        c = torch.nn.functional.softplus(alpha.max(-1).values) > float(threshold)
+        cell = torch.zeros(X, Y, Z, dtype=torch.bool, device=c.device)
+        for dx in (0, 1):
+            for dy in (0, 1):
+                for dz in (0, 1):
+                    cell |= c[dx:dx + X, dy:dy + Y, dz:dz + Z]
+        return cls.from_mask(cls.dilate_mask(cell, dilate), lo, hi)
 
 
 def sparsification_plot(var_vec, err_vec, uncert_type='c', err_type='rmse'):

@@ -149,7 +149,7 @@ enum {
                                            optional members are NULL the backward launches exactly the kernels it launches without the flag: the
                                            parameter gradient, d_rays and d_z are the same bits.  cfnerf_workspace_bytes does not change.  Every other
                                            entry point that takes flags refuses it.  Without the flag every argument means what it meant */
-    CFNERF_F_SEAM_GRAD  = 0x400         /* (= 1 << 10, bit 10) cfnerf_composite_bwd also differentiates raw2outputs in z_vals and rays_d (RUN:424-429, 447:
+    CFNERF_F_SEAM_GRAD  = 0x400,        /* (= 1 << 10, bit 10) cfnerf_composite_bwd also differentiates raw2outputs in z_vals and rays_d (RUN:424-429, 447:
                                            in the reference raw2outputs(raw, z_vals, rays_d) is a graph in all three arguments - the link a script that
                                            refines poses needs when it injects a network_query_fn of its own).  cfnerf_composite_bwd takes no flags:
                                            the bit is passed in its `white_bkgd` ARGUMENT, and the background is white iff (white_bkgd & ~0x400) != 0,
@@ -160,6 +160,20 @@ enum {
                                            call (the same bits); d_z_vals / d_rays_d by a second launch that reads raw once more, skipped when neither
                                            is wanted, as the first is when d_raw is not.  No atomics: bit-reproducible.  Every entry point that takes
                                            `flags` refuses the bit.  Without the bit the call is what it was */
+    CFNERF_F_CULL       = 0x800         /* (= 1 << 11, bit 11) render through an occupancy grid: samples in empty cells never reach the network.  An
+                                           EVALUATION path (inference only, no backward) over the unfused seam, with no new entry point:
+                                             cfnerf_sample_points with the flag reads its `pts` ARGUMENT as a pointer to a HOST struct cfnerf_cull (below) -
+                                               the caller passes (float*)&cull - and writes z_vals as always plus the keep / skip decision of every sample
+                                               and the compact list of the kept points, in (ray, sample) order;
+                                             cfnerf_embed and cfnerf_network_fwd run on that list as on any P' points;
+                                             cfnerf_composite_fwd takes the bit in its `white_bkgd` ARGUMENT - the background is white iff
+                                               (white_bkgd & ~0x800) != 0, so every value a caller passes today means what it meant - and then reads raw as
+                                               [P',K,4], rows for the kept samples only, and its `weights_opt` ARGUMENT as a pointer to a HOST struct
+                                               cfnerf_sparse_raw (below), (float*)&sp.
+                                           The caller learns P' by reading ray_start[N] back: ONE device-to-host copy per call, which SYNCHRONISES - the
+                                           "nothing synchronises" contract of the train step does not cover this path and is not affected by it.  The
+                                           compaction is deterministic (no atomics).  cfnerf_composite_bwd does not take the bit.  Every entry point that takes
+                                           `flags` other than cfnerf_sample_points refuses it.  Without the bit every call is what it was */
 };
 
 /* The cotangents of a CFNERF_F_COTANGENTS backward: a HOST struct of DEVICE pointers, passed in place of d_rgb_map. */
@@ -176,6 +190,30 @@ typedef struct cfnerf_composite_grads {
     float* d_z_vals;                    /* [N,S]     or NULL */
     float* d_rays_d;                    /* [N,3]     or NULL */
 } cfnerf_composite_grads;
+
+/* The occupancy grid and the outputs of a CFNERF_F_CULL cfnerf_sample_points: a HOST struct of DEVICE pointers, passed in place of pts;
+ * read during the call, not kept.  The grid is X*Y*Z cells on the box from `lo`; the cell of a point is, per axis,
+ * floorf((p - lo) * scale) in fp32 (subtract, multiply, floor - nothing else), p with the bits the plain call writes to pts; the point is
+ * inside iff 0 <= cell < res on all three axes.  A sample is KEPT iff its cell's bit is set; outside the box (or NaN) `outside` decides. */
+typedef struct cfnerf_cull {
+    const uint32_t* occ_bits;           /* X*Y*Z bits; cell (ix,iy,iz) is bit ((ix*Y+iy)*Z+iz) & 31 of word ((ix*Y+iy)*Z+iz) >> 5 */
+    float   lo[3];                      /* corner of cell (0,0,0) */
+    float   scale[3];                   /* res[d] / (hi[d] - lo[d]), computed by the HOST in fp32 */
+    int32_t res[3];                     /* X, Y, Z cells (each >= 1) */
+    int32_t outside;                    /* 0: a point outside the box (or NaN) is KEPT, 1: culled */
+    int32_t* slot;                      /* [N,S] out: row of the sample in the compact list, -1 = culled */
+    int64_t* ray_start;                 /* [N+1] out: exclusive scan of the per-ray kept counts; ray_start[N] = P' */
+    float*   pts_c;                     /* [N*S,3] out: the first P' rows are written, in (ray, sample) order */
+    int32_t* ray_of;                    /* [N*S] out: the ray of each compact row (the first P' entries are written) */
+} cfnerf_cull;
+
+/* Where the rows of a CFNERF_F_CULL cfnerf_composite_fwd's raw [P',K,4] belong: a HOST struct of DEVICE pointers, passed in place of
+ * weights_opt; read during the call, not kept. */
+typedef struct cfnerf_sparse_raw {
+    const int32_t* slot;                /* [N,S] as written by cfnerf_sample_points */
+    const int64_t* ray_start;           /* [N+1] */
+    float* weights_opt;                 /* [N,S,K] or NULL; a culled sample's weights are written as 0 */
+} cfnerf_sparse_raw;
 
 CFNERF_API int         cfnerf_version(void);
 CFNERF_API const char* cfnerf_last_error(void);
@@ -220,7 +258,13 @@ CFNERF_API int cfnerf_ndc_rays(int H, int W, float focal, float near_, const flo
 CFNERF_API int cfnerf_embed(const float* x, int64_t P, int multires, float* out, cfnerf_stream s);
 
 /* replaces: the sampling lines of render_rays as a standalone call, RUN:510-534 (used by the unfused query path):
- * rays [N,11], t_vals [S], t_rand [N,S] or NULL, LINDISP flag -> z_vals [N,S], pts [N,S,3]                      */
+ * rays [N,11], t_vals [S], t_rand [N,S] or NULL, LINDISP flag -> z_vals [N,S], pts [N,S,3]
+ * With CFNERF_F_CULL (evaluation only) pts is (float*)&cull of a host struct cfnerf_cull: z_vals [N,S] is written with the bits of the call
+ * without the flag (t_rand and CFNERF_F_LINDISP are honoured), and through the struct slot [N,S], ray_start [N+1], the kept points
+ * pts_c [P',3] (the bits of the plain call's pts, in (ray, sample) order) and ray_of [P'].  The capacity N * S (< 2^31) always fits: the call
+ * cannot overflow.  P' = ray_start[N] is on the device: reading it is one synchronising device-to-host copy per call.  Three launches (count,
+ * a scan over the N rays, emit), no atomics.  A NULL struct, a NULL occ_bits, slot, ray_start, pts_c or ray_of, or a res below 1 is refused
+ * before anything touches a device.                                                                                                        */
 CFNERF_API int cfnerf_sample_points(const float* rays, const float* t_vals, const float* t_rand, int flags, int64_t N, int S,
                          float* z_vals, float* pts, cfnerf_stream s);
 
@@ -291,7 +335,13 @@ CFNERF_API int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* 
                        float* raw, float* entropy_out, cfnerf_stream s);
 
 /* replaces: raw2outputs() RUN:411-454 as a standalone call.  raw [N,S,K,4] (16-byte aligned, S * K * 16 bytes per ray < 2 GiB: it is
- * fetched through one buffer descriptor per ray), z_vals [N,S], rays_d [N,3]; any K >= 1, any S >= 1 */
+ * fetched through one buffer descriptor per ray), z_vals [N,S], rays_d [N,3]; any K >= 1, any S >= 1
+ * With CFNERF_F_CULL or-ed into white_bkgd (evaluation only; the background is white iff (white_bkgd & ~0x800) != 0) raw is [P',K,4], the rows
+ * of the kept samples alone in (ray, sample) order, and weights_opt is (float*)&sp of a host struct cfnerf_sparse_raw naming slot, ray_start
+ * and the weights proper.  The maps and weights are, bit for bit, those of the plain call on the dense raw [N,S,K,4] in which every culled
+ * sample has the density latent -1e4 (softplus gives exactly 0 there): a culled sample contributes alpha = 0.  Only the sign of slot is
+ * read; a ray's rows are fetched through a descriptor of exactly its block [ray_start[ray], ray_start[ray + 1]), so inconsistent indices
+ * read zeros, never another ray's rows.  A NULL struct, slot or ray_start is refused.  No backward: cfnerf_composite_bwd does not take the bit. */
 CFNERF_API int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d,
                          int64_t N, int S, int K, int white_bkgd,
                          float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
