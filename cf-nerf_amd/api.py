@@ -1294,6 +1294,207 @@ def render_rays_culled(ray_batch, network_fn, grid, t_vals=None, lindisp=False, 
     return ret
 
 
+# --------------------------------------------------------------------------------------------
+# Sampling through an occupancy grid (evaluate.OccupancySampler): the grid as a SAMPLING AID on the fused path, train and eval.  All S
+# depths of a ray are placed inside the occupied part of it; the render is the existing explicit-depth launch (z_vals), so stash, backward,
+# ray gradient and slices are the ones the hierarchical extension uses.  The ray probes are the cull kernel (no synchronising copy); the
+# depth warp is elementwise torch on N x (2 bins + 1 + S) values, like the sampling adjoint of the unfused seam - no kernel, flag or
+# struct member is added.
+_WARP_PROBE_BYTES = 256 << 20      # bound of the buffers of one probe launch: _cull_launch allocates 24 bytes per probe
+_PROBE_T_CACHE = {}
+
+
+def _probe_t_vals(bins, device):
+    """``linspace(0, 1, 2 bins + 1)`` (made on the CPU, one device copy per ``(bins, device)`` - read-only)"""
+    key = (int(bins), str(torch.device(device)))
+    t = _PROBE_T_CACHE.get(key)
+    if t is None:
+        t = _PROBE_T_CACHE[key] = torch.linspace(0., 1., steps=2 * int(bins) + 1).to(device)
+    return t
+
+
+def warp_probe_chunk(bins):
+    """Rays of one probe launch of ``warp_z_vals``: as many as keep its buffers (24 bytes per probe) under 256 MiB"""
+    return max(1, (_WARP_PROBE_BYTES // 24) // (2 * int(bins) + 1))
+
+
+def bins_from_probes(probes, pad=0):
+    """The bin rule of ``warp_z_vals`` in torch (any device): ``probes [N, 2 bins + 1]`` bool -> ``[N, bins]`` bool.  Bin ``b`` is occupied iff
+    probe ``2b``, ``2b + 1`` or ``2b + 2`` is (its two ends and its middle); the result is grown by ``pad`` bins on both sides along the ray
+    (a 1-D max-pool)."""
+    b = probes[:, 0:-1:2] | probes[:, 1::2] | probes[:, 2::2]
+    pad = int(pad)
+    if pad > 0 and b.shape[1] > 0:
+        b = torch.nn.functional.max_pool1d(b[:, None].to(torch.float32), kernel_size=2 * pad + 1, stride=1, padding=pad)[:, 0] > 0
+    return b
+
+
+def bins_from_probes_reference(probes, pad=0):
+    """``bins_from_probes`` as a plain numpy loop (tests)"""
+    import numpy as np
+    probes = np.asarray(probes, dtype=bool)
+    N, B = probes.shape[0], (probes.shape[1] - 1) // 2
+    raw = np.zeros((N, B), dtype=bool)
+    for n in range(N):
+        for b in range(B):
+            raw[n, b] = probes[n, 2 * b] or probes[n, 2 * b + 1] or probes[n, 2 * b + 2]
+    out = raw.copy()
+    for n in range(N):
+        for b in range(B):
+            if raw[n, b]:
+                out[n, max(b - int(pad), 0):b + int(pad) + 1] = True
+    return out
+
+
+def probe_occupancy_reference(pts, grid, outside="cull"):
+    """The cell rule of the cull kernel restated in fp32 torch on the CPU (tests): ``pts [N,P,3]`` -> ``[N,P]`` bool.  The cell of a point is
+    ``floor((p - lo) * scale)`` per axis (subtract, multiply, floor - each rounded to fp32), inside iff ``0 <= cell < res``, occupied iff its
+    bit of ``grid.bits`` is set; a point outside the box is occupied iff ``outside == "keep"``.  A point on a cell face belongs to the upper cell."""
+    pts = pts.detach().to("cpu", torch.float32)
+    lo, scale = torch.tensor(grid.lo), torch.tensor(grid.scale)
+    res = torch.tensor(grid.res, dtype=torch.float32)
+    t = torch.floor((pts - lo) * scale)
+    inside = ((t >= 0) & (t < res)).all(-1)
+    i = torch.where(inside[..., None], t, torch.zeros_like(t)).long()
+    cell = (i[..., 0] * grid.res[1] + i[..., 1]) * grid.res[2] + i[..., 2]
+    words = grid.bits.detach().to("cpu", torch.int64)
+    occ = ((words[cell >> 5] >> (cell & 31)) & 1).bool()
+    return torch.where(inside, occ, torch.full_like(occ, outside == "keep"))
+
+
+def warp_from_bins(z_plain, near, far, bins):
+    """The depth warp of ``warp_z_vals`` as a pure torch function (any device; fp32): ``z_plain [N,S]`` (non-decreasing along a ray),
+    ``near`` / ``far [N]``, ``bins [N,B]`` bool -> ``(z_vals [N,S], n_occ [N] int32)``.  With ``n`` = occupied bins of the ray:
+
+        f = clamp((z_plain - near) / (far - near), 0, 1);  target = f n;  i = min(floor(target), n - 1);  r = target - i
+        b = index of the i-th occupied bin (0-based, ascending);  z = near + (far - near) (b + r) / B
+
+    i.e. the share ``f`` of the ray's length becomes the same share of its OCCUPIED length.  A ray with ``n == 0`` or ``n == B`` keeps
+    ``z_plain`` bit for bit.  Every step is monotone, so ``z`` is non-decreasing like ``z_plain``."""
+    N, B = bins.shape
+    near, far = near.reshape(N, 1).to(torch.float32), far.reshape(N, 1).to(torch.float32)
+    z_plain = z_plain.to(torch.float32)
+    csum = bins.to(torch.int64).cumsum(1)                            # occupied bins up to and including b
+    n = csum[:, -1:] if B > 0 else csum.new_zeros(N, 1)
+    nf = n.to(torch.float32)
+    target = ((z_plain - near) / (far - near)).clamp(0., 1.) * nf
+    i = torch.minimum(torch.floor(target), (nf - 1.).clamp_min(0.))
+    r = target - i
+    b = torch.searchsorted(csum, i.to(torch.int64) + 1).clamp_max(max(B - 1, 0))       # the first bin with i + 1 occupied bins up to it
+    z = near + (far - near) * ((b.to(torch.float32) + r) / float(B))
+    return torch.where((n == 0) | (n == B), z_plain, z), n.reshape(N).to(torch.int32)
+
+
+def warp_z_vals_reference(z_plain, near, far, bins):
+    """The rules of ``warp_from_bins`` as a plain fp64 numpy loop (tests): ``(z_vals [N,S] float64, n_occ [N])``.  ``z_plain`` / ``near`` /
+    ``far`` are read as they are given (the fp32 values of the device, widened)."""
+    import numpy as np
+    z_plain = np.asarray(z_plain, dtype=np.float64)
+    near, far = np.asarray(near, dtype=np.float64).reshape(-1), np.asarray(far, dtype=np.float64).reshape(-1)
+    bins = np.asarray(bins, dtype=bool)
+    (N, S), B = z_plain.shape, bins.shape[1]
+    out, n_occ = z_plain.copy(), np.zeros(N, dtype=np.int64)
+    for k in range(N):
+        occ = np.flatnonzero(bins[k])
+        n = n_occ[k] = len(occ)
+        if n == 0 or n == B:
+            continue
+        for s in range(S):
+            f = min(max((z_plain[k, s] - near[k]) / (far[k] - near[k]), 0.0), 1.0)
+            target = f * n
+            i = min(int(np.floor(target)), n - 1)
+            out[k, s] = near[k] + (far[k] - near[k]) * (occ[i] + (target - i)) / B
+    return out, n_occ
+
+
+@torch.no_grad()
+def warp_z_vals(ray_batch, sampler, t_vals=None, t_rand=None, lindisp=False):
+    """Depths of the packed rays ``ray_batch [N,11]`` placed inside the occupied part of every ray, for an ``evaluate.OccupancySampler``:
+    ``{'z_vals' [N,S], 'n_occ' [N] int32, 'bins' [N,bins] bool}``.  Nothing is copied to the host and nothing synchronises.
+
+    * Probes: ``2 bins + 1`` depths per ray, ``near (1 - t) + far t`` for ``t = linspace(0, 1, 2 bins + 1)`` (no jitter, never ``lindisp``),
+      tested by the cull kernel (cfnerf_sample_points with CFNERF_F_CULL: its cell rule, faces included); a probe is occupied iff its
+      ``slot >= 0``.  Rays are probed ``warp_probe_chunk(bins)`` at a time so that the probe buffers stay under 256 MiB.
+    * Bins: ``bins_from_probes`` - bin ``b`` is occupied iff probe ``2b``, ``2b + 1`` or ``2b + 2`` is, then grown by ``sampler.pad``.
+    * Plain depths: ``z_plain [N,S]`` = what cfnerf_sample_points writes for ``t_vals`` / ``t_rand`` / ``lindisp`` (RUN:510-532), bit for bit.
+    * Warp: ``warp_from_bins``.  A ray with no occupied bin, or with all of them, keeps ``z_plain`` bit for bit: a full grid reproduces the
+      dense sampling, an empty ray renders as before.
+
+    The depths are CONSTANTS of the graph, as ``sample_pdf``'s are: nothing is differentiated through the warp.
+
+    Quadrature.  The composite gives a sample the interval up to the NEXT sample (``dists``, RUN:426), so the last sample before a gap
+    integrates its density over the whole gap.  With ``pad >= 1``, or a grid that was dilated (``OccupancyGrid.from_network(dilate >= 1)``),
+    that sample sits in the low-density margin of an occupied run and the gap contributes next to nothing; with ``pad = 0`` on a tight grid
+    it sits inside the object and the gap is rendered as solid.  Use one of the two (the sampler's default is ``pad = 1``)."""
+    _need_gpu(ray_batch, "ray_batch")
+    rays = _f32c(ray_batch)
+    if rays.dim() != 2 or rays.shape[1] != 11:
+        raise ValueError(f"ray_batch must be [N,11], got {tuple(rays.shape)}")
+    dev = rays.device
+    t_vals = t_vals_table(dev) if t_vals is None else t_vals.to(dev, torch.float32).contiguous()
+    t_rand = None if t_rand is None else _f32c(t_rand.to(dev))
+    N, B = rays.shape[0], int(sampler.bins)
+    if N == 0:
+        return {'z_vals': torch.empty(0, t_vals.shape[0], device=dev), 'n_occ': torch.empty(0, dtype=torch.int32, device=dev),
+                'bins': torch.empty(0, B, dtype=torch.bool, device=dev)}
+    z_plain, _ = _sample_points(rays, t_vals, t_rand, lindisp)
+    tp, step = _probe_t_vals(B, dev), warp_probe_chunk(B)
+    parts = [bins_from_probes(_cull_launch(rays[i:i + step], sampler.grid, tp, None, False, sampler.outside)[1] >= 0, sampler.pad)
+             for i in range(0, N, step)]
+    bins = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+    z, n_occ = warp_from_bins(z_plain, rays[:, 6], rays[:, 7], bins)
+    return {'z_vals': z, 'n_occ': n_occ, 'bins': bins}
+
+
+def render_rays_warped(ray_batch, network_fn, sampler, is_train, lindisp=False, perturb=0., white_bkgd=False, t_rand=None, eps_alpha=None,
+                       eps_rgb=None, t_vals=None, retweights=False, chunk=None):
+    """``render_rays`` with its depths warped into the occupied part of every ray (``warp_z_vals`` with an ``evaluate.OccupancySampler``), in
+    ONE fused explicit-depth launch - the launches of the hierarchical extension's fine pass: ``_RenderFn`` under autograd (parameter
+    gradients, and ``ray_batch.grad`` when the rays ask for one, as for any explicit-depth launch; the depths are constants), the plain
+    forward otherwise.  Returns the dict of the fused ``render_rays`` (``rgb_map [N,3,K]``, ``disp_map`` / ``depth_map [N,K]``; ``raw``,
+    ``loss_entropy``, ``pts`` when ``is_train``; ``weights`` with ``retweights``) plus ``z_vals [N,S]`` and ``n_occ [N]``.  Latents as in
+    ``render_rays``, ``latent_draws = "netchunk"`` (with its ray cut ``chunk``) included; ``t_rand`` / ``perturb`` jitter the plain depths the
+    warp starts from."""
+    _need_gpu(ray_batch, "ray_batch")
+    if ray_batch.dim() != 2 or ray_batch.shape[-1] != 11:
+        raise ValueError("ray_batch must be [N,11] = o3,d3,near,far,viewdir3 (use_viewdirs=True)")
+    model = _unwrap(network_fn)
+    dev = ray_batch.device
+    t_vals = t_vals_table(dev) if t_vals is None else t_vals.to(dev, torch.float32).contiguous()
+    N, S, K = ray_batch.shape[0], t_vals.shape[0], model.K_samples
+    rays = _f32c(ray_batch)
+    want_rays = torch.is_grad_enabled() and ray_batch.requires_grad
+    explicit = LT.pack(eps_alpha, eps_rgb)
+    if is_train:
+        tr, eps, _ = LT.train_latents(model.latent_draws, explicit, N=N, S=S, K=K, netchunk=model.netchunk, chunk=chunk, perturb=perturb,
+                                      own_t_rand=t_rand is not None)
+        t_rand, eps = (tr if t_rand is None else t_rand), LT.to_device(eps, dev)
+    else:
+        eps = _latents(model, explicit, False, dev)
+    if perturb > 0.:
+        t_rand = _f32c((torch.rand([N, S]) if t_rand is None else t_rand).to(dev))
+    else:
+        t_rand = None
+    w = warp_z_vals(rays, sampler, t_vals, t_rand, lindisp)
+    z = w['z_vals']
+    flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_TRAIN if is_train else 0)
+    model._sync()
+    if N > 0 and (want_rays or (is_train and torch.is_grad_enabled() and model.flat.requires_grad)):
+        # (rays that ask for a gradient on the eval branch: the stashed train-branch launch on the eval latents, as in render_rays)
+        rgb_map, disp, depth, ent, raw, pts, wts = _RenderFn.apply(model.flat, model, ray_batch.to(torch.float32) if want_rays else rays, t_vals,
+                                                                   None, eps, flags | L.F_TRAIN, is_train, z, bool(retweights))
+        o = {'rgb_map': rgb_map, 'disp_map': disp, 'depth_map': depth, 'raw': raw, 'entropy': ent, 'pts': pts, 'weights': wts}
+    else:
+        o = _render_fwd(model, rays, t_vals, None, eps, flags, z_vals=z, raw=is_train, weights=retweights, pts=is_train)
+    ret = {k: o[k] for k in ('rgb_map', 'disp_map', 'depth_map')}
+    if is_train:
+        ret.update(raw=o['raw'], loss_entropy=o['entropy'].reshape(1, 1, 1).expand(N * S, K, 1), pts=o['pts'])
+    if retweights:
+        ret['weights'] = o['weights']
+    ret.update(z_vals=z, n_occ=w['n_occ'])
+    return ret
+
+
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """RUN:88-100."""
     all_ret = {}

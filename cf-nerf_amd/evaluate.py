@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, render, render_rays_culled, t_vals_table
+from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, render, render_rays_culled, t_vals_table, warp_probe_chunk, warp_z_vals
 
 
 def render_path_train(render_poses, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0):
@@ -119,14 +119,20 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
 
     ``occupancy=`` an ``OccupancyGrid`` (``stats="basic"`` only) renders through the grid instead (CFNERF_F_CULL, ``api.render_rays_culled``):
     samples in empty cells never reach the network.  The rays are walked in bounded chunks, each with one synchronising copy of its kept
-    count, and the keys above are derived in torch from the per-K maps of the sparse composite, with the same estimators."""
+    count, and the keys above are derived in torch from the per-K maps of the sparse composite, with the same estimators.
+
+    ``occupancy=`` an ``OccupancySampler`` (``grid.sampler()``; ``stats="basic"`` only) SAMPLES through the grid on the fused path instead:
+    per ray chunk ``api.warp_z_vals`` places all S depths inside the occupied part of the ray and one explicit-depth fused launch writes
+    the ``[n,8]`` statistics (no per-K map leaves the chip unless ``want_maps``; nothing synchronises).  Adds ``occupied_bins``, the mean of
+    ``n_occ / bins`` over the rays (a device scalar)."""
     if stats not in ("basic", "ext", "geometry"):
         raise ValueError(f"stats must be 'basic', 'ext' or 'geometry', got {stats!r}")
     if occupancy is not None:
         if stats != "basic":
             raise ValueError(f"occupancy= supports stats='basic' only, got {stats!r}: the culled path ends in the standalone composite, which has "
                              "no acc_map (the accumulated opacity of stats='ext' / 'geometry' exists in the fused kernels alone)")
-        return _render_uncertainty_culled(H, W, focal, c2w, network_fn, occupancy, near, far, ndc, lindisp, white_bkgd, rows, want_maps, t_vals, gt)
+        route = _render_uncertainty_warped if isinstance(occupancy, OccupancySampler) else _render_uncertainty_culled
+        return route(H, W, focal, c2w, network_fn, occupancy, near, far, ndc, lindisp, white_bkgd, rows, want_maps, t_vals, gt)
     if stats == "geometry":
         if want_maps or gt is not None:
             raise ValueError("stats='geometry' renders no colour: want_maps / gt are not arguments of it (api.render_geometry gives the per-K maps)")
@@ -229,6 +235,38 @@ def _render_uncertainty_culled(H, W, focal, c2w, network_fn, grid, near, far, nd
         out.update(rgb_map=rgb_map.reshape(h, W, 3, K), disp_map=disp_map.reshape(h, W, K), depth_map=depth_map.reshape(h, W, K))
     if gt is not None:
         sq = (rgb_mean - gt.to(dev, torch.float32).reshape(n, 3)) ** 2
+        out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
+    return out
+
+
+def _render_uncertainty_warped(H, W, focal, c2w, network_fn, sampler, near, far, ndc, lindisp, white_bkgd, rows, want_maps, t_vals, gt):
+    """``render_uncertainty(occupancy=sampler)``: per ray chunk ``api.warp_z_vals``, then one fused explicit-depth launch with kstats.  The
+    chunk keeps the probe buffers of the warp under 256 MiB (``api.warp_probe_chunk``)."""
+    net = _unwrap(network_fn)
+    dev = net.device
+    K = net.K_samples
+    r0, r1 = rows if rows is not None else (0, H)
+    n, h = (r1 - r0) * W, r1 - r0
+    t_vals = t_vals_table(dev) if t_vals is None else t_vals.to(dev, torch.float32).contiguous()
+    packed = _pack_rays(H, W, focal, c2w=c2w, n=n, pixel0=r0 * W, ndc=ndc, near=near, far=far, device=dev)
+    net._sync()
+    eps = net.eval_eps()
+    flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
+    kst, n_occ = torch.empty(n, 8, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    maps = [torch.empty(n, 3, K, device=dev), torch.empty(n, K, device=dev), torch.empty(n, K, device=dev)] if want_maps else None
+    step = warp_probe_chunk(sampler.bins)
+    for i in range(0, n, step):
+        w = warp_z_vals(packed[i:i + step], sampler, t_vals, None, lindisp)
+        o = _render_fwd(net, packed[i:i + step], t_vals, None, eps, flags, z_vals=w['z_vals'], maps=want_maps, kstats=True, entropy=False)
+        kst[i:i + step], n_occ[i:i + step] = o['kstats'], w['n_occ']
+        if want_maps:
+            maps[0][i:i + step], maps[1][i:i + step], maps[2][i:i + step] = o['rgb_map'], o['disp_map'], o['depth_map']
+    out = dict(rgb_mean=kst[:, 0:3].reshape(h, W, 3), rgb_unc=kst[:, 3:6].reshape(h, W, 3), disp_mean=kst[:, 6].reshape(h, W),
+               depth_mean=kst[:, 7].reshape(h, W), occupied_bins=(n_occ.to(torch.float32) / float(sampler.bins)).mean())
+    if want_maps:
+        out.update(rgb_map=maps[0].reshape(h, W, 3, K), disp_map=maps[1].reshape(h, W, K), depth_map=maps[2].reshape(h, W, K))
+    if gt is not None:
+        sq = (kst[:, 0:3] - gt.to(dev, torch.float32).reshape(n, 3)) ** 2
         out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
     return out
 
@@ -356,6 +394,29 @@ class OccupancyGrid:
                 for dz in (0, 1):
                     cell |= c[dx:dx + X, dy:dy + Y, dz:dz + Z]
         return cls.from_mask(cls.dilate_mask(cell, dilate), lo, hi)
+
+    def sampler(self, **kw):
+        """An ``OccupancySampler`` on this grid (``bins``, ``pad``, ``outside``)"""
+        return OccupancySampler(self, **kw)
+
+
+class OccupancySampler:
+    """How rays are SAMPLED through an ``OccupancyGrid`` (``api.warp_z_vals``, ``api.render_rays_warped``, ``Trainer.step(occupancy=)``,
+    ``render_uncertainty(occupancy=)``): every ray is cut into ``bins`` equal depth bins between its own near and far (columns 6, 7 of the
+    packed ray), a bin is occupied iff one of three probe depths in it lies in an occupied cell, occupied runs are grown by ``pad`` bins on
+    both sides along the ray (a 1-D max-pool; 0 = none), and all S depths of the ray are placed in the occupied bins.  ``outside`` =
+    ``"cull"`` / ``"keep"`` is the probe's answer outside the grid's box, as in ``api.cull_points``.  ``1 <= bins <= 4096``."""
+
+    def __init__(self, grid, bins=512, pad=1, outside="cull"):
+        if not isinstance(grid, OccupancyGrid):
+            raise TypeError("OccupancySampler needs an OccupancyGrid")
+        if int(bins) != bins or not 1 <= int(bins) <= 4096:
+            raise ValueError(f"bins must be an integer in [1, 4096], got {bins!r}")
+        if int(pad) != pad or int(pad) < 0:
+            raise ValueError(f"pad must be an integer >= 0, got {pad!r}")
+        if outside not in ("keep", "cull"):
+            raise ValueError(f"outside must be 'keep' or 'cull', got {outside!r}")
+        self.grid, self.bins, self.pad, self.outside = grid, int(bins), int(pad), outside
 
 
 def sparsification_plot(var_vec, err_vec, uncert_type='c', err_type='rmse'):

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib as L
 from . import latents as LT
-from .api import NeRF_Flows, _f32c, _pack_rays, _unwrap, t_vals_table
+from .api import NeRF_Flows, _f32c, _pack_rays, _unwrap, t_vals_table, warp_z_vals
 
 
 def backward_available() -> bool:
@@ -364,7 +364,7 @@ class Trainer:
 
     def forward_backward(self, H, W, focal, rays, target, t_rand=None, eps=None, near=0., far=1., ndc=True,
                          lindisp=False, white_bkgd=False, perturb=1., t_vals=None, eps_chunks=None, depth_rays=None, target_depth=None,
-                         **_ignored):
+                         occupancy=None, **_ignored):
         """Forward + loss + backward of this rank's shard.  Leaves the (un-reduced) gradient in ``self.grad``.
 
         ``depth_rays [2,N_d,3]`` / ``target_depth [N_d]`` (this rank's shard of the step's key-point rays, ``depth_lambda > 0``): the launch
@@ -372,7 +372,12 @@ class Trainer:
         the KDE-NLL runs on the colour rows, the depth term on the depth rows; ``self.depth_loss`` holds the rank's contribution to the
         step's ``depth_loss`` and ``self.scalars[0]`` includes ``depth_lambda`` times it.  The entropy term is the launch's (all rays);
         in netchunk mode on a batch of several network calls it is the FIRST call's alone, as in the reference (RUN:1024 cuts the
-        per-point entropy tensor to its first N rows): that call is one launch, the rest a second one without an entropy cotangent."""
+        per-point entropy tensor to its first N rows): that call is one launch, the rest a second one without an entropy cotangent.
+
+        ``occupancy=`` an ``evaluate.OccupancySampler``: the depths of all the step's rays (depth rays included) are warped ONCE into the
+        occupied part of every ray (``api.warp_z_vals`` on the plain depths of ``t_vals`` / ``t_rand`` / ``lindisp``; constants of the graph)
+        and every pass is the explicit-depth launch on its rows of them - slices, depth rays, ``ray_grad``, both precisions and netchunk
+        latents as without.  ``self.z_vals [N,S]`` and ``self.n_occ [N]`` are left for the caller.  Without it nothing changes."""
         net = self.net
         dev = net.flat.device
         t_vals = t_vals_table(dev) if t_vals is None else t_vals            # (cached per device)
@@ -404,6 +409,11 @@ class Trainer:
         t_rand = None if perturb <= 0. else _f32c(torch.rand(N, S, device=dev) if t_rand is None else t_rand).to(dev)
         eps = LT.to_device(_f32c(eps), dev)
         self._eps_rows = eps if eps.dim() == 3 else None
+        z_vals = None
+        if occupancy is not None:                                           # grid-guided sampling: the jitter went into the plain depths
+            w = warp_z_vals(self.packed, occupancy, t_vals, t_rand, lindisp)
+            self.z_vals, self.n_occ = w['z_vals'], w['n_occ']
+            z_vals, t_rand = self.z_vals, None
         net._sync()
         flags = L.F_TRAIN | (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
         n_sl = self.n_slices(N)
@@ -414,7 +424,7 @@ class Trainer:
         if self.ray_grad:
             self._ray_grad_buffers(N, S, max(first, N - first) if first is not None else N // n_sl)
         if first is not None:
-            return self._first_call_and_rest(first, N, t_vals, t_rand, eps, S, flags, target, depth)
+            return self._first_call_and_rest(first, N, t_vals, t_rand, eps, S, flags, target, depth, z_vals)
         Ns = N // n_sl
         net.ensure_workspace(Ns, S, K)
         if n_sl == 1:
@@ -428,7 +438,7 @@ class Trainer:
             sc_sum, ent_sum = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         for i in range(n_sl):
             self._pass(i * Ns, (i + 1) * Ns, t_vals, t_rand, eps, S, flags, target, self.beta1 / (self.world * n_sl), sc, ent, d_ent,
-                       grad=self.grad, accumulate=i > 0, depth=depth, ray_grad=self.ray_grad)
+                       grad=self.grad, accumulate=i > 0, depth=depth, ray_grad=self.ray_grad, z_vals=z_vals)
             if n_sl > 1:
                 sc_sum += sc
                 ent_sum += ent
@@ -438,7 +448,7 @@ class Trainer:
             self.entropy.copy_(ent_sum / n_sl)
         return self.grad
 
-    def _first_call_and_rest(self, first, N, t_vals, t_rand, eps, S, flags, target, depth):
+    def _first_call_and_rest(self, first, N, t_vals, t_rand, eps, S, flags, target, depth, z_vals=None):
         """Depth-supervised netchunk step on a batch of several network calls (one process): rows [0, first) - the first network call -
         with the entropy term ``beta1`` * (that call's entropy), rows [first, N) without one; the second launch's gradient is added
         to the first's and the colour rows' scalar contributions add like slices'."""
@@ -446,9 +456,9 @@ class Trainer:
         self.net.ensure_workspace(max(first, N - first), S, self.net.K_samples)
         sc, ent = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         self._pass(0, first, t_vals, t_rand, eps, S, flags, target, self.beta1, self.scalars, self.entropy, self.d_ent, grad=self.grad,
-                   depth=depth, ray_grad=self.ray_grad)
+                   depth=depth, ray_grad=self.ray_grad, z_vals=z_vals)
         self._pass(first, N, t_vals, t_rand, eps, S, flags, target, 0.0, sc, ent, None, grad=self.grad, accumulate=True, depth=depth,
-                   ray_grad=self.ray_grad)
+                   ray_grad=self.ray_grad, z_vals=z_vals)
         sc[:3] += self.scalars[:3]
         self.scalars[:3] = sc[:3]
         self.scalars[3] = -10.0 * torch.log10(sc[2])                        # HLP:16 on the batch's mse
@@ -493,9 +503,9 @@ class Trainer:
 
     def step(self, H, W, focal, rays, target, **kw):
         """One full train step.  Returns the device tensor [loss, loss_nll, mse, psnr] of the local shard (``depth_rays=`` /
-        ``target_depth=``: the depth-supervised step, see forward_backward)."""
+        ``target_depth=``: the depth-supervised step; ``occupancy=`` a sampler: sampling through an occupancy grid - see forward_backward)."""
         kw = {k: v for k, v in kw.items() if k in ("t_rand", "eps", "eps_chunks", "near", "far", "ndc", "lindisp", "white_bkgd", "perturb",
-                                                     "t_vals", "depth_rays", "target_depth")}
+                                                     "t_vals", "depth_rays", "target_depth", "occupancy")}
         return self._step(self.forward_backward, self._exchange, H, W, focal, rays, target, kw)
 
     # ---- EXTENSION (not in the reference, SURVEY R1 / 8f-4): coarse + fine sampling through the single network -----
@@ -511,6 +521,9 @@ class Trainer:
             raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
         if depth_rays is not None or target_depth is not None:
             raise NotImplementedError("depth rays are not supported by the hierarchical-sampling extension")
+        if _ignored.get("occupancy") is not None:
+            raise NotImplementedError("occupancy= (sampling through an occupancy grid) is not supported by forward_backward_hierarchical / "
+                                      "step_hierarchical: both choose the depths of the pass; use step(occupancy=)")
         net = self.net
         dev = net.flat.device
         N, K, S, Ni = rays[1].reshape(-1, 3).shape[0], net.K_samples, int(N_samples), int(N_importance)
@@ -551,6 +564,9 @@ class Trainer:
         """One full train step of the coarse + fine EXTENSION (see forward_backward_hierarchical)."""
         if self.latent_draws == "netchunk":
             raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
+        if kw.get("occupancy") is not None:
+            raise NotImplementedError("occupancy= (sampling through an occupancy grid) is not supported by step_hierarchical: both choose "
+                                      "the depths of the pass; use step(occupancy=)")
         # always the plain one-bucket all-reduce: this gradient is grad_fine + grad_c, added by torch after the last backward, while
         # the early-range event that overlap_comm's first bucket waits for fires inside that backward, before the add
         return self._step(self.forward_backward_hierarchical, lambda: allreduce_sum_(self.gbuf, self.world, self.group, self.force_allreduce),
