@@ -3,11 +3,12 @@
 //   cull_scan_kernel          exclusive scan of the N counts (ray_start [N+1], ray_start[N] = P')
 //   cull_kernel<true>         emit pass: z_vals, slot, the compact point list pts_c and ray_of
 //   composite_sparse_kernel   raw2outputs on raw rows that exist for the kept samples only
-// The existing kernels are not touched: what is shared comes from the inline device functions of cfnerf_device.h.
+// What is shared with the other kernels comes from the inline device functions of cfnerf_device.h and, for the composite, cfnerf_composite.h and the text of cfnerf_comp_fwd_body.h.
 //
 // Compaction is deterministic - (ray, sample) order, no atomics: one wave per ray with lane = sample as in sample_points_kernel, a
 // 64-sample chunk's keep mask is one ballot, a lane's rank the popcount of the mask bits below it.
 #include "cfnerf_device.h"
+#include "cfnerf_composite.h"
 #include "cfnerf_kernels.h"
 
 namespace cfnerf {
@@ -124,127 +125,20 @@ void cull_scan_kernel(int64_t* __restrict__ ray_start, int64_t N) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// composite_kernel (cfnerf_fwd.hip) on a COMPACT raw: lane = sample, the same scans, the same sums, chunk by chunk; only the fetch differs.
+// composite_kernel (cfnerf_fwd.hip) on a COMPACT raw: the same text (cfnerf_comp_fwd_body.h, CFN_COMP_SPARSE 1); only the fetch differs.
 // A ray's kept rows are contiguous in raw_c, [ray_start[ray], ray_start[ray + 1]); the buffer descriptor covers exactly that block, so
 // whatever `slot` holds, a load returns this ray's rows or zeros - never another ray's memory, never an unmapped page.  A chunk's staged
 // block starts at the chunk's first kept row; a kept lane reads row rank(sample) of it, a culled lane contributes alpha = 0: the
 // transmittance factor (1 - 0) + 1e-10f == 1.0f and every sum gets + 0.0f, both exact, so the maps carry the bits of composite_kernel on
 // the dense raw whose culled samples have the density latent -1e4 (softplus gives exactly 0 there in both transcendental modes).
-constexpr int kCompSparseKB = 64;      // latents of one pass over a ray's chunks: kCompKB of composite_kernel (K above it takes a second pass)
 template <int KG, bool FAST>
 __global__ __launch_bounds__(kThreads, FAST ? 4 : 3)
 void composite_sparse_kernel(const float* __restrict__ raw_c, const int32_t* __restrict__ slot, const int64_t* __restrict__ ray_start,
                              const float* __restrict__ z_vals, const float* __restrict__ rays_d, int64_t N, int S, int K, int white_bkgd,
                              float* rgb_map, float* disp_map, float* depth_map, float* weights) {
-    using M = Num<FAST>;
-    using St = CompStage<KG>;
-    __shared__ __attribute__((aligned(16))) float stage_all[kWaves][St::kQuads * 4];
-    __shared__ float sums_all[kWaves][6][kCompSparseKB];
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int64_t ray = (int64_t)blockIdx.x * kWaves + wave;
-    if (ray >= N) return;                                    // (no workgroup barrier below: a wave leaves alone)
-    float* stage = stage_all[wave];
-    float (*sums)[kCompSparseKB] = sums_all[wave];
-    const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)stage);
-    const float* d = rays_d + ray * 3;
-    const float dnorm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    const float* zr = z_vals + ray * (int64_t)S;
-    const int32_t* sr = slot + ray * (int64_t)S;
-    // the ray's block of raw_c, clamped to [0, P'] and to S rows: a descriptor of exactly its bytes (S * K * 16 < 2 GiB is checked by the host)
-    const int64_t total = max(ray_start[N], (int64_t)0);
-    const int64_t r0 = min(max(ray_start[ray], (int64_t)0), total);
-    const int64_t rows = raw_c == nullptr ? 0 : min(max(ray_start[ray + 1] - r0, (int64_t)0), min((int64_t)S, total - r0));      // (no raw: P' = 0)
-    const i32x4 rsrc = ds_rsrc(raw_c + r0 * (int64_t)K * 4, (int)rows * K * 16);
-    const int nch = (S + 63) / 64;
-    const bool vec_w = weights != nullptr && (K & 3) == 0;
-    unsigned voff[KG];
-#pragma unroll
-    for (int j = 0; j < KG; ++j) voff[j] = St::piece_voff(lane, j, K);
-    for (int kb = 0; kb < K; kb += kCompSparseKB) {
-        const int kn = min(K - kb, kCompSparseKB);
-        sums[0][lane] = 1.f;
-#pragma unroll
-        for (int c = 1; c < 6; ++c) sums[c][lane] = 0.f;
-        int row_ch = 0;                                      // kept rows of the chunks in front of this one
-        for (int ch = 0; ch < nch; ++ch) {
-            const int s = ch * 64 + lane;
-            const bool valid = s < S;
-            float zv = 0.f, dist = 0.f;
-            bool keep = false;
-            if (valid) {
-                zv = zr[s];
-                const float dz = (s == S - 1) ? 1e1f : zr[s + 1] - zv;
-                dist = dz * dnorm;
-                keep = sr[s] >= 0;
-            }
-            const uint64_t mask = __builtin_amdgcn_ballot_w64(keep);
-            const int cnt = __popcll(mask);
-            if (cnt == 0 && weights == nullptr) continue;    // (uniform) an empty chunk multiplies every carry by 1.0f and adds 0.0f to every sum
-            const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-            const int my_q0 = rank * KG, my_swz = St::swz(rank);
-            for (int gi = 0; gi < kn; gi += KG) {
-                const int g0 = kb + gi;
-                // St::fetch with the chunk's first KEPT row in place of its first sample
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                wave_lds_turn();
-                const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane((row_ch * K + g0) * 16);
-#pragma unroll
-                for (int j = 0; j < KG; ++j) ds_dma16(rsrc, lds0 + j * 1024, voff[j], soff);
-                // lane q < KG: latent g0 + q
-                const int sl = gi + (lane < KG ? lane : 0);
-                float carv = sums[0][sl], acc0 = sums[1][sl], acc1 = sums[2][sl], acc2 = sums[3][sl], accd = sums[4][sl], acca = sums[5][sl];
-                St::landed();
-                float wv[KG];
-#pragma unroll
-                for (int q = 0; q < KG; ++q) {
-                    wv[q] = 0.f;
-                    if (gi + q < kn) {                       // (uniform)
-                        const f32x4 rv = *reinterpret_cast<const f32x4*>(stage + (my_q0 + (q ^ my_swz)) * 4);
-                        const float car = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(carv), q));
-                        const float alpha = keep ? 1.f - M::exp(-M::softplus(rv[3]) * dist) : 0.f;
-                        const float xk = (1.f - alpha) + 1e-10f;
-                        float incl, excl;
-                        comp_scan_mul(xk, incl, excl);
-                        const float wgt = alpha * (car * excl);
-                        wv[q] = wgt;
-                        const float c0 = keep ? wgt * M::sigmoid(rv[0]) : 0.f, c1 = keep ? wgt * M::sigmoid(rv[1]) : 0.f,
-                                    c2 = keep ? wgt * M::sigmoid(rv[2]) : 0.f;
-                        const float s0 = comp_sum(c0), s1 = comp_sum(c1), s2 = comp_sum(c2);
-                        const float sd = comp_sum(wgt * zv), sa = comp_sum(wgt);
-                        const float carn = car * comp_last(incl);
-                        if (lane == q) { acc0 += s0; acc1 += s1; acc2 += s2; accd += sd; acca += sa; carv = carn; }
-                    }
-                }
-                if (lane < KG) { sums[0][sl] = carv; sums[1][sl] = acc0; sums[2][sl] = acc1; sums[3][sl] = acc2; sums[4][sl] = accd; sums[5][sl] = acca; }
-                if (weights != nullptr && valid) {
-                    float* wrow = weights + (ray * S + s) * (int64_t)K + g0;
-                    if (vec_w) {
-#pragma unroll
-                        for (int q = 0; q < KG; q += 4)
-                            if (gi + q < kn) { f32x4 o; o[0] = wv[q]; o[1] = wv[q + 1]; o[2] = wv[q + 2]; o[3] = wv[q + 3]; *reinterpret_cast<f32x4*>(wrow + q) = o; }
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < KG; ++q)
-                            if (gi + q < kn) wrow[q] = wv[q];
-                    }
-                }
-            }
-            row_ch += cnt;
-        }
-        wave_lds_turn();
-        if (lane < kn) {                                     // lane l: latent kb + l
-            const int k = kb + lane;
-            float r0c = sums[1][lane], r1c = sums[2][lane], r2c = sums[3][lane];
-            const float rd = sums[4][lane], ra = sums[5][lane];
-            if (white_bkgd) { r0c = r0c + (1.f - ra); r1c = r1c + (1.f - ra); r2c = r2c + (1.f - ra); }
-            float* o = rgb_map + ray * 3 * (int64_t)K;
-            o[0 * K + k] = r0c; o[1 * K + k] = r1c; o[2 * K + k] = r2c;
-            disp_map[ray * (int64_t)K + k] = 1.f / fmaxf(1e-10f + 1e-10f, rd / (ra + 1e-10f) + 1e-10f);
-            depth_map[ray * (int64_t)K + k] = rd;
-        }
-        wave_lds_turn();
-    }
+#define CFN_COMP_SPARSE 1
+#include "cfnerf_comp_fwd_body.h"
+#undef CFN_COMP_SPARSE
 }
 
 // ---- host launchers (cfnerf_kernels.h)

@@ -713,8 +713,9 @@ __device__ __forceinline__ float wave_prev_dpp(float v, float identity) { return
 __device__ __forceinline__ float wave_last(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
 __device__ __forceinline__ float wave_sum_dpp(float v) { return wave_last(wave_scan_add_dpp(v)); }     // (same in every lane: an SGPR)
 
-// The cross-lane steps of the composite and of its adjoint, in ONE place: the fused forward / tail kernels and the standalone
-// composite_kernel / composite_bwd_kernel must use the same arithmetic (the unfused seam's gradients are held to the fused path's to 1e-6).
+// The cross-lane steps of the composite and of its adjoint, in ONE place: the fused forward / tail kernels and the stand-alone
+// composite kernels (their walk around these steps: cfnerf_composite.h) must use the same arithmetic (the unfused seam's gradients are
+// held to the fused path's to 1e-6).
 __device__ __forceinline__ void comp_scan_mul(float xk, float& incl, float& excl) {     // inclusive / exclusive running product over the lanes
     if (kUseDpp) { incl = wave_scan_mul_dpp(xk); excl = wave_prev_dpp(incl, 1.f); }
     else { incl = wave_scan_mul(xk); excl = __shfl_up(incl, 1, 64); if (lane_id() == 0) excl = 1.f; }
@@ -891,37 +892,12 @@ __device__ __forceinline__ void ds_dma16(i32x4 rsrc, unsigned lds_addr, unsigned
                  : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
 
-// ---- a wave's private LDS block as a turntable (standalone composite kernels: cfnerf_fwd.hip / cfnerf_bwd.hip)
+// ---- a wave's private LDS block as a turntable (the stand-alone composite kernels' staged block, CompStage, is in cfnerf_composite.h)
 // A wave's own LDS queue is in order; this only keeps the COMPILER from moving LDS accesses across the point where lanes exchange data.
 __device__ __forceinline__ void wave_lds_turn() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// The [64 samples][KG latents] block of quads (16 bytes = one (sample, latent) entry of raw [N,S,K,4]) of a 64-sample chunk, filled by
-// KG LDS-DMA pieces: piece j, lane l lands at quad position p = 64 j + l.  Position p = sl * KG + c holds latent kk = c ^ swz(sl) of
-// sample sl: the KG lanes of a sample still cover its one 16 KG-byte segment of global memory (every piece is 1 KB of full cache lines
-// when K is a multiple of KG), and the transposed read - lane = sample, one latent - touches 16 different bank quads per 16 lanes.
-template <int KG> struct CompStage {
-    static_assert(KG == 4 || KG == 8, "a sample's segment is 64 or 128 bytes");
-    static constexpr int kQuads = 64 * KG;
-    static __device__ __forceinline__ int swz(int sl) { return (sl / (16 / KG)) & (KG - 1); }
-    // this lane's byte offset (inside the chunk's rows of the ray, group 0) of the quad it moves in piece j
-    static __device__ __forceinline__ unsigned piece_voff(int lane, int j, int K) {
-        const int p = j * 64 + lane, sl = p / KG, kk = (p % KG) ^ swz(sl);
-        return (unsigned)((sl * K + kk) * 16);
-    }
-    static __device__ __forceinline__ void fetch(i32x4 rsrc, unsigned lds0, const unsigned (&voff)[KG], int ch, int g0, int K) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the previous block's LDS reads have their data
-        wave_lds_turn();
-        const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane((ch * 64 * K + g0) * 16);
-#pragma unroll
-        for (int j = 0; j < KG; ++j) ds_dma16(rsrc, lds0 + j * 1024, voff[j], soff);
-    }
-    static __device__ __forceinline__ void landed() {            // (hipcc does not count asm memory operations: explicit wait)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_lds_turn();
-    }
-};
 
 }  // namespace cfnerf

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "cfnerf_device.h"
+#include "cfnerf_composite.h"
 #include "cfnerf_kernels.h"
 
 namespace cfnerf {
@@ -1245,146 +1246,21 @@ __global__ void entropy_finalize_kernel(const float* partials, int n_part, const
 // Reads 16*S*K + 4*S + 12 bytes per ray, writes 20*K (+4*S*K for weights).  `raw [N,S,K,4]` has the latent index inside the sample
 // index, so "lane = sample, one k at a time" (rounds 1-3) read 16 bytes per lane at a stride of 16 K bytes and came back K times for
 // the rest of every cache line (0.9 TB/s at K = 32).  Now a wave takes KG latents at a time: the [64 samples][KG latents] block of a
-// chunk arrives by LDS-DMA as KG fully coalesced 1-KB pieces into the wave's own LDS block (CompStage, cfnerf_device.h: no staging
+// chunk arrives by LDS-DMA as KG fully coalesced 1-KB pieces into the wave's own LDS block (CompStage, cfnerf_composite.h: no staging
 // registers, conflict-free transposed reads) and the KG latents are walked out of LDS with the arithmetic of rounds 1-3 (= the fused
 // kernel's composite) operation for operation; a latent's carry and sums wait in LDS between the chunks (entry = lane), so the maps
 // leave as one store per output.
 // Transcendentals like the fused kernels: libm below kFastFlowsK latents (there the kernel is bound by libm's instruction count,
 // not by memory), the hardware forms from there on (Num<FAST>).
-constexpr int kCompKB = 64;       // latents of one pass over a ray's chunks (their carries and sums wait in LDS, entry = lane)
+// The body is cfnerf_comp_fwd_body.h, shared as text with composite_sparse_kernel (cfnerf_cull.hip, CFN_COMP_SPARSE 0 / 1).
 template <int KG, bool FAST>
 __global__ __launch_bounds__(kThreads, FAST ? 4 : 3)      // (the LDS block leaves room for 4 workgroups per CU: keep the registers there too)
 void composite_kernel(const float* __restrict__ raw, const float* __restrict__ z_vals, const float* __restrict__ rays_d,
                       int64_t N, int S, int K, int white_bkgd, float* rgb_map, float* disp_map, float* depth_map,
                       float* weights) {
-    using M = Num<FAST>;
-    using St = CompStage<KG>;
-    constexpr int U = (KG == 8) ? 4 : 1;                     // groups per round of the weights turn-around (32 latents = one 128-byte line per sample)
-    __shared__ __attribute__((aligned(16))) float stage_all[kWaves][St::kQuads * 4];
-    __shared__ float sums_all[kWaves][6][kCompKB];           // [0] transmittance entering the next chunk, [1..5] rgb / depth / acc sums
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int64_t ray = (int64_t)blockIdx.x * kWaves + wave;
-    if (ray >= N) return;                                    // (no workgroup barrier below: a wave leaves alone)
-    float* stage = stage_all[wave];
-    float (*sums)[kCompKB] = sums_all[wave];
-    const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)stage);
-    const float* d = rays_d + ray * 3;
-    const float dnorm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    const float* zr = z_vals + ray * (int64_t)S;
-    const i32x4 rsrc = ds_rsrc(raw + ray * (int64_t)S * K * 4, S * K * 16);      // samples past S arrive as zeros (bounds check)
-    const int nch = (S + 63) / 64;
-    const bool vec_w = weights != nullptr && (K & 3) == 0;   // a lane's KG weights of a sample as 16-byte stores
-    unsigned voff[KG];
-#pragma unroll
-    for (int j = 0; j < KG; ++j) voff[j] = St::piece_voff(lane, j, K);
-    const int my_q0 = lane * KG, my_swz = St::swz(lane);
-    // Chunk-major: all latents of a chunk before the next chunk, so that raw streams through once front to back and the KG-float
-    // pieces a group adds to a sample's row of `weights` complete their cache lines while these are still in L2.
-    for (int kb = 0; kb < K; kb += kCompKB) {
-        const int kn = min(K - kb, kCompKB);
-        sums[0][lane] = 1.f;
-#pragma unroll
-        for (int c = 1; c < 6; ++c) sums[c][lane] = 0.f;
-        for (int ch = 0; ch < nch; ++ch) {
-            const int s = ch * 64 + lane;
-            const bool valid = s < S;
-            float zv = 0.f, dist = 0.f;
-            if (valid) {
-                zv = zr[s];
-                const float dz = (s == S - 1) ? 1e1f : zr[s + 1] - zv;
-                dist = dz * dnorm;
-            }
-            for (int gf = 0; gf < kn; gf += KG * U) {
-                float wrow_keep[KG * U];                     // (U > 1) this sample's weights of up to 32 latents, for full-line stores
-#pragma unroll
-                for (int i = 0; i < KG * U; ++i) wrow_keep[i] = 0.f;
-#pragma unroll
-                for (int gq = 0; gq < U; ++gq) {
-                const int gi = gf + gq * KG;
-                if (gi >= kn) continue;                      // (uniform)
-                const int g0 = kb + gi;
-                St::fetch(rsrc, lds0, voff, ch, g0, K);
-                // lane q < KG: latent g0 + q
-                const int slot = gi + (lane < KG ? lane : 0);
-                float carv = sums[0][slot], acc0 = sums[1][slot], acc1 = sums[2][slot], acc2 = sums[3][slot], accd = sums[4][slot], acca = sums[5][slot];
-                St::landed();
-                float wv[KG];
-#pragma unroll
-                for (int q = 0; q < KG; ++q) {
-                    wv[q] = 0.f;
-                    if (gi + q < kn) {                       // (uniform)
-                        const f32x4 rv = *reinterpret_cast<const f32x4*>(stage + (my_q0 + (q ^ my_swz)) * 4);
-                        const float car = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(carv), q));
-                        const float alpha = valid ? 1.f - M::exp(-M::softplus(rv[3]) * dist) : 0.f;
-                        const float xk = (1.f - alpha) + 1e-10f;
-                        float incl, excl;
-                        comp_scan_mul(xk, incl, excl);
-                        const float wgt = alpha * (car * excl);
-                        wv[q] = wgt;
-                        const float s0 = comp_sum(wgt * M::sigmoid(rv[0])), s1 = comp_sum(wgt * M::sigmoid(rv[1])), s2 = comp_sum(wgt * M::sigmoid(rv[2]));
-                        const float sd = comp_sum(wgt * zv), sa = comp_sum(wgt);
-                        const float carn = car * comp_last(incl);
-                        if (lane == q) { acc0 += s0; acc1 += s1; acc2 += s2; accd += sd; acca += sa; carv = carn; }   // (chunk by chunk like the fused kernel)
-                    }
-                }
-                if (lane < KG) { sums[0][slot] = carv; sums[1][slot] = acc0; sums[2][slot] = acc1; sums[3][slot] = acc2; sums[4][slot] = accd; sums[5][slot] = acca; }
-                if (U > 1 && vec_w) {
-#pragma unroll
-                    for (int q = 0; q < KG; ++q) wrow_keep[gq * KG + q] = wv[q];
-                } else if (weights != nullptr && valid) {
-                    float* wrow = weights + (ray * S + s) * (int64_t)K + g0;
-                    if (vec_w) {                             // (K <= 4: a sample's row is one 16-byte store, rows adjacent)
-#pragma unroll
-                        for (int q = 0; q < KG; q += 4)
-                            if (gi + q < kn) { f32x4 o; o[0] = wv[q]; o[1] = wv[q + 1]; o[2] = wv[q + 2]; o[3] = wv[q + 3]; *reinterpret_cast<f32x4*>(wrow + q) = o; }
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < KG; ++q)
-                            if (gi + q < kn) wrow[q] = wv[q];
-                    }
-                }
-                }
-                if (U > 1 && vec_w) {
-                    // Up to 32 latents = 128 bytes per sample: turned around in the (now free) LDS block so that 8 lanes write one sample's
-                    // full line - a lane's own 16- or 32-byte pieces at a pitch of 4 K bytes took 414 instead of ~290 us at K = 32
-                    // (a timing-only build with a contiguous layout).  Quad kq of sample sl sits at sl * 8 + (kq ^ swz(sl)).
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    wave_lds_turn();
-#pragma unroll
-                    for (int kq = 0; kq < 8; ++kq) {
-                        f32x4 o; o[0] = wrow_keep[kq * 4]; o[1] = wrow_keep[kq * 4 + 1]; o[2] = wrow_keep[kq * 4 + 2]; o[3] = wrow_keep[kq * 4 + 3];
-                        *reinterpret_cast<f32x4*>(stage + (lane * 8 + (kq ^ my_swz)) * 4) = o;
-                    }
-                    wave_lds_turn();
-                    float* wblk = weights + (ray * S + (int64_t)ch * 64) * K + kb + gf;
-                    f32x4 ov[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int sl = j * 8 + (lane >> 3), kq = lane & 7;
-                        ov[j] = *reinterpret_cast<const f32x4*>(stage + (sl * 8 + (kq ^ St::swz(sl))) * 4);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int sl = j * 8 + (lane >> 3), kq = lane & 7;
-                        if (ch * 64 + sl < S && gf + kq * 4 < kn) *reinterpret_cast<f32x4*>(wblk + (int64_t)sl * K + kq * 4) = ov[j];
-                    }
-                }
-            }
-        }
-        wave_lds_turn();
-        if (lane < kn) {                                     // lane l: latent kb + l
-            const int k = kb + lane;
-            float r0 = sums[1][lane], r1 = sums[2][lane], r2 = sums[3][lane];
-            const float rd = sums[4][lane], ra = sums[5][lane];
-            if (white_bkgd) { r0 = r0 + (1.f - ra); r1 = r1 + (1.f - ra); r2 = r2 + (1.f - ra); }
-            float* o = rgb_map + ray * 3 * (int64_t)K;
-            o[0 * K + k] = r0; o[1 * K + k] = r1; o[2 * K + k] = r2;
-            disp_map[ray * (int64_t)K + k] = 1.f / fmaxf(1e-10f + 1e-10f, rd / (ra + 1e-10f) + 1e-10f);
-            depth_map[ray * (int64_t)K + k] = rd;
-        }
-        wave_lds_turn();
-    }
+#define CFN_COMP_SPARSE 0
+#include "cfnerf_comp_fwd_body.h"
+#undef CFN_COMP_SPARSE
 }
 
 

@@ -10,7 +10,9 @@ dilate settings and, for ONE 800 x 800 view per K, reports
   * the same with an all-ones grid: the overhead of the route by itself,
   * mean and maximum absolute difference to the dense image in rgb_mean and depth_mean, and the PSNR of both against ground truth.
 
-    python tests/tools/culled_eval_bench.py [--steps 1500] [--size 800] [--repeats 5] [--ks 32,4]"""
+    python tests/tools/culled_eval_bench.py [--steps 1500] [--size 800] [--repeats 5] [--ks 32,4] [--grids all | all-ones]
+
+--grids all-ones: the all-ones grid alone (an A/B of the route's own kernels, e.g. the sparse composite of two builds)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -125,6 +127,7 @@ def main():
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--ks", default="32,4")
+    ap.add_argument("--grids", default="all", choices=("all", "all-ones"))
     a = ap.parse_args()
     size, focal = a.size, PS.FOCAL * a.size / PS.H               # the scene's vertical field of view at size x size
     c2w = PS.pose_spherical(10.0, -25.0, 4.0)                    # a view between the training poses
@@ -139,7 +142,7 @@ def main():
                           "dense_render_uncertainty_ms": round(dense_ms, 2), "dense_psnr": psnr(dense["rgb_mean"], gt)}), flush=True)
         packed = A._pack_rays(size, size, focal, c2w=c2w, n=size * size, ndc=False, near=PS.NEAR, far=PS.FAR, device=net.device)
         settings = [("all-ones", None, 1, 0)] + [("network", th, res, dil) for th, res, dil in ((0.5, 64, 1), (0.05, 64, 1), (0.05, 128, 1), (0.01, 128, 2))]
-        for kind, th, res, dil in settings:
+        for kind, th, res, dil in settings[:1] if a.grids == "all-ones" else settings:
             if kind == "all-ones":
                 grid, build_ms = E.OccupancyGrid.from_mask(torch.ones(1, 1, 1, dtype=torch.bool), BOX_LO, BOX_HI), 0.0      # the route's overhead by itself
             else:
