@@ -13,12 +13,6 @@
 
 namespace cfnerf {
 
-// (RUN:512 / 514: the lines of zlin_f in cfnerf_fwd.hip, restated - the sampled depths must carry the bits of sample_points_kernel)
-__device__ __forceinline__ float cull_zlin(float t, float nearv, float farv, bool lindisp) {
-    if (lindisp) return 1.f / ((1.f / nearv) * (1.f - t) + (1.f / farv) * t);
-    return nearv * (1.f - t) + farv * t;
-}
-
 // The cell of a coordinate: floorf((p - lo) * scale), inside iff 0 <= t < res.  Exactly this fp32 arithmetic (the library is built with
 // -ffp-contract=off: subtract, multiply, floor) - tests/test_hip_cull.py restates it in torch and asks for agreement on cell faces too.
 // A NaN fails both comparisons: outside.
@@ -53,17 +47,7 @@ void cull_kernel(const CullArgs A) {
         for (int ch = 0; ch < nch; ++ch) {
             const int s = ch * 64 + lane;
             const bool valid = s < S;
-            const int sc = min(s, S - 1);
-            // the depth of sample_points_kernel, operation for operation
-            const float tc = t_vals[sc], tp = t_vals[min(sc + 1, S - 1)], tm = t_vals[max(sc - 1, 0)];
-            const float tr = (t_rand != nullptr) ? t_rand[n * S + sc] : 0.f;
-            const float zc = cull_zlin(tc, nearv, farv, lind);
-            float zv = zc;
-            if (t_rand != nullptr) {
-                const float upper = (sc == S - 1) ? zc : 0.5f * (cull_zlin(tp, nearv, farv, lind) + zc);
-                const float lower = (sc == 0) ? zc : 0.5f * (zc + cull_zlin(tm, nearv, farv, lind));
-                zv = lower + (upper - lower) * tr;
-            }
+            const float zv = strat_depth(t_vals, t_rand, n, S, min(s, S - 1), nearv, farv, lind);      // the depth of sample_points_kernel: its function
             const float p0 = o0 + d0 * zv, p1 = o1 + d1 * zv, p2 = o2 + d2 * zv;                          // RUN:534: the bits of `pts`
             int ix, iy, iz;
             const bool in0 = cull_cell(p0, A.lo[0], A.scale[0], A.res[0], ix);

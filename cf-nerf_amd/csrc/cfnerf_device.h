@@ -598,6 +598,28 @@ __device__ __forceinline__ void store_tiles(const f32x16 (&acc)[2][NTW], const S
         store_tiles_impl<NTW, ACT, PREC, WANT_BITS, 0, BIAS_IN_ACC>(acc, s, nt0, nts, wp, lds_dst, ld, col0, gdst, gld, rows_valid, mbits, bias_pre);
 }
 
+// ---- the sampled depths along a ray (RUN:510-532), one statement of the rule for every kernel that samples -------------------------------
+__device__ __forceinline__ float zlin_f(float t, float nearv, float farv, bool lindisp) {
+    if (lindisp) return 1.f / ((1.f / nearv) * (1.f - t) + (1.f / farv) * t);       // RUN:514
+    return nearv * (1.f - t) + farv * t;                                            // RUN:512
+}
+// the jitter of RUN:518-532 on a sample's plain depth zc: tp / tm are the table entries of its neighbours (not used at the ray's ends), tr its t_rand
+// (sample_pdf_kernel, cfnerf_fwd.hip, states the same three lines with conditional loads of tp / tm: the one other copy)
+__device__ __forceinline__ float strat_jitter(float zc, float tp, float tm, float tr, bool first, bool last, float nearv, float farv, bool lindisp) {
+    const float upper = last ? zc : 0.5f * (zlin_f(tp, nearv, farv, lindisp) + zc);
+    const float lower = first ? zc : 0.5f * (zc + zlin_f(tm, nearv, farv, lindisp));
+    return lower + (upper - lower) * tr;
+}
+// lane = sample (sample_points_kernel, cull_kernel): the depth of sample `sc` of ray n, sc already clamped to S - 1 - every operand is requested
+// before the first is used, with clamped neighbours (the selects of strat_jitter take what an unclamped walk computes)
+__device__ __forceinline__ float strat_depth(const float* __restrict__ t_vals, const float* __restrict__ t_rand, int64_t n, int S, int sc,
+                                             float nearv, float farv, bool lindisp) {
+    const float tc = t_vals[sc], tp = t_vals[min(sc + 1, S - 1)], tm = t_vals[max(sc - 1, 0)];
+    const float tr = (t_rand != nullptr) ? t_rand[n * S + sc] : 0.f;
+    const float zc = zlin_f(tc, nearv, farv, lindisp);
+    return (t_rand != nullptr) ? strat_jitter(zc, tp, tm, tr, sc == 0, sc == S - 1, nearv, farv, lindisp) : zc;
+}
+
 // ---- elementwise numerics: the same definitions torch uses on the reference path ---------------
 __device__ __forceinline__ float softplus_f(float x) {        // F.softplus(beta=1, threshold=20)
     return x > 20.f ? x : log1pf(expf(x));

@@ -44,11 +44,6 @@ __host__ __device__ inline size_t fwd_lds_bytes(int W, int ha, int K) {
     return sizeof(float) * ((size_t)kTileM * act_ld(W) + (size_t)kTileM * (ha + 4) + 68 * 4 + 32 + 16 + (size_t)comp_rows(K) * 8);
 }
 
-__device__ __forceinline__ float zlin_f(float t, float nearv, float farv, bool lindisp) {
-    if (lindisp) return 1.f / ((1.f / nearv) * (1.f - t) + (1.f / farv) * t);       // RUN:514
-    return nearv * (1.f - t) + farv * t;                                            // RUN:512
-}
-
 // positional encoding of the tile into act[:, 0:64)   (HLP:42-51, RUN:70-71)
 template <int MODE, int LD, int PREC, int NTHR>
 __device__ __forceinline__ void encode_tile(float* act, const float* rowinfo, const float* __restrict__ x, int64_t p0,
@@ -141,6 +136,57 @@ __device__ __forceinline__ void kstats_ext_epilogue(const float* comp, int K, in
 struct FwdKargs { FwdArgs A; NetTab T; };
 static_assert(offsetof(FwdKargs, T) == (sizeof(FwdArgs) + alignof(NetTab) - 1) / alignof(NetTab) * alignof(NetTab), "kernarg layout");
 
+// ---- the scaffolding of the two forward kernels, fused_fwd_kernel and geom_fwd_kernel (kGeom), written once -------------------------
+// The arguments live in the kernarg segment, so every per-layer descriptor read is a scalar load from constant
+// memory.  (Through a global pointer the compiler must assume the kernel's own stores may alias the table and issues
+// VECTOR loads with a full wait in front of each layer's first operand fetch: two or three dependent L2 round trips.)
+// They are read PER PHASE through CFN_PHASE_ARGS (kernarg_fresh, cfnerf_device.h), not held in registers across the tile loop.
+// The few scalars every phase needs (sizes, the wave index, the operand pointers) stay in SGPRs, but a phase takes them through
+// sgpr_fresh: what the optimiser DERIVES from them (row offsets rr * HR * 4 of a slab store, wave * 32, LDS sub-pointers ...) is then
+// recomputed on the scalar unit inside the phase instead of being hoisted in front of the tile loop and spilt as well.
+// CFN_FWD_KERNEL_LOCALS + CFN_PHASE_LOCALS are the device-side spelling of the LDS layout of fwd_lds_bytes; the geometry kernel uses neither
+// the h_rgb size nor gdir / red, and its comp rows hold (_ _ _ depth acc T disp _).
+#define CFN_KARGS const CFN_KCONST FwdKargs* kq_ = kernarg_fresh<FwdKargs>(); const CFN_KCONST FwdArgs& A = kq_->A; const CFN_KCONST NetTab& T = kq_->T
+#define CFN_PHASE_LOCALS(F)                                                                                                              \
+    [[maybe_unused]] const int HA = F(HA0), HR = kGeom ? 0 : F(HR0), HLD = HA + 4, S = F(S0), K = F(K0), ic = F(ic0), icv = F(icv0), wave = F(wave0);  \
+    [[maybe_unused]] const int chunks_per_ray = (S + kTileM - 1) / kTileM, Dn = F(Dn0), skip_l = F(skip0);                                \
+    [[maybe_unused]] float* const rowinfo = hs + kTileM * HLD; /* [65][4]: x y z zval */                                                  \
+    [[maybe_unused]] float* const gdir = rowinfo + 68 * 4;     /* [32] */                                                                 \
+    [[maybe_unused]] float* const red = gdir + 32;             /* [16] */                                                                 \
+    [[maybe_unused]] float* const comp = red + 16;             /* [comp_rows(K)][8]: r g b depth acc T disp _ */                          \
+    [[maybe_unused]] const float* __restrict__ const wp = F(wp0);                                                                          \
+    [[maybe_unused]] const __bf16* __restrict__ const wp16 = F(wp160)
+#define CFN_PHASE_ARGS CFN_KARGS; CFN_PHASE_LOCALS(sgpr_fresh)
+// kernel scope: the workgroup's shape, the LDS tile, the launch's sizes and its number of units (rays / 64-point tiles)
+#define CFN_FWD_KERNEL_LOCALS                                                                                                            \
+    (void)A_; (void)T_;                                                                                                                  \
+    CFN_KARGS;                                                                                                                           \
+    using C = FwdCfg<W>;                                                                                                                 \
+    constexpr int LD = C::LD;                                                                                                            \
+    constexpr int kWv = C::NWV, kThr = C::NTHR;     /* waves / threads of this width's workgroup */                                      \
+    extern __shared__ __attribute__((aligned(16))) float smem[];                                                                         \
+    [[maybe_unused]] const int HA0 = T.ha_sz, HR0 = kGeom ? 0 : T.hr_sz;                                                                  \
+    float* const act = smem;                                                                                                             \
+    float* const hs = act + kTileM * LD;      /* then rowinfo | gdir | red | comp: CFN_PHASE_LOCALS */                                   \
+    [[maybe_unused]] const int tid = threadIdx.x, lane = lane_id(), wave0 = wave_id();                                                    \
+    const float* const wp0 = A.wp;                                                                                                       \
+    const __bf16* const wp160 = reinterpret_cast<const __bf16*>(A.wp16);                                                                 \
+    const int S0 = A.S, K0 = A.K;                                                                                                        \
+    const int ic0 = T.ic, icv0 = T.icv;                                                                                                  \
+    const int Dn0 = T.D, skip0 = T.skip;                                                                                                 \
+    const int64_t n_units = (MODE == 0) ? A.N : (A.P + kTileM - 1) / kTileM
+// top of the unit loop: the phase scalars and (ray mode) the unit's ray `r` - origin, direction, near / far, |d|
+#define CFN_FWD_UNIT_RAY                                                                                                                 \
+        float ro[3], rd[3], nearv = 0.f, farv = 1.f, dnorm = 0.f;                                                                        \
+        CFN_PHASE_ARGS;                                                                                                                  \
+        [[maybe_unused]] const float* const r = A.rays + unit * 11;                                                                      \
+        if (MODE == 0) {                                                                                                                 \
+            _Pragma("unroll")                                                                                                            \
+            for (int d = 0; d < 3; ++d) { ro[d] = r[d]; rd[d] = r[3 + d]; }                                                              \
+            nearv = r[6]; farv = r[7];                                                                                                   \
+            dnorm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);   /* torch.norm(rays_d) RUN:429 */                          \
+        }
+
 // Q4 (train, fp32, whole tiles only - launch_fused_fwd picks the variant from FwdArgs::q4): the trunk activations h[0 .. D-1], 8 of the 9.5
 // W-wide units the forward stashes per point, leave as Q4 pieces straight from the accumulator registers (cfnerf_device.h) instead of by
 // rows out of LDS.
@@ -155,41 +201,8 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
     static_assert(!Q4 || (TRAIN && PREC == PREC_F32), "the Q4 stash layout exists for the fp32 train variants only");
     static_assert(!ROWS || TRAIN, "latent rows are a train-branch mode");
     static_assert(!EXT || (MODE == 0 && !Q4 && !ROWS), "the extended K-statistics belong to ray launches without a stash and without latent rows");
-    // The arguments live in the kernarg segment, so every per-layer descriptor read is a scalar load from constant
-    // memory.  (Through a global pointer the compiler must assume the kernel's own stores may alias the table and issues
-    // VECTOR loads with a full wait in front of each layer's first operand fetch: two or three dependent L2 round trips.)
-    // They are read PER PHASE through CFN_PHASE_ARGS (kernarg_fresh, cfnerf_device.h), not held in registers across the tile loop.
-    // The few scalars every phase needs (sizes, the wave index, the operand pointers) stay in SGPRs, but a phase takes them through
-    // sgpr_fresh: what the optimiser DERIVES from them (row offsets rr * HR * 4 of a slab store, wave * 32, LDS sub-pointers ...) is then
-    // recomputed on the scalar unit inside the phase instead of being hoisted in front of the tile loop and spilt as well.
-#define CFN_PHASE_LOCALS(F)                                                                                                              \
-    [[maybe_unused]] const int HA = F(HA0), HR = F(HR0), HLD = HA + 4, S = F(S0), K = F(K0), ic = F(ic0), icv = F(icv0), wave = F(wave0);  \
-    [[maybe_unused]] const int chunks_per_ray = (S + kTileM - 1) / kTileM, Dn = F(Dn0), skip_l = F(skip0);                                \
-    [[maybe_unused]] float* const rowinfo = hs + kTileM * HLD; /* [65][4]: x y z zval */                                                  \
-    [[maybe_unused]] float* const gdir = rowinfo + 68 * 4;     /* [32] */                                                                 \
-    [[maybe_unused]] float* const red = gdir + 32;             /* [16] */                                                                 \
-    [[maybe_unused]] float* const comp = red + 16;             /* [comp_rows(K)][8]: r g b depth acc T disp _ */                          \
-    [[maybe_unused]] const float* __restrict__ const wp = F(wp0);                                                                          \
-    [[maybe_unused]] const __bf16* __restrict__ const wp16 = F(wp160)
-    (void)A_; (void)T_;
-#define CFN_KARGS const CFN_KCONST FwdKargs* kq_ = kernarg_fresh<FwdKargs>(); const CFN_KCONST FwdArgs& A = kq_->A; const CFN_KCONST NetTab& T = kq_->T
-#define CFN_PHASE_ARGS CFN_KARGS; CFN_PHASE_LOCALS(sgpr_fresh)
-    CFN_KARGS;
-    using C = FwdCfg<W>;
-    constexpr int LD = C::LD;
-    constexpr int kWv = C::NWV, kThr = C::NTHR;     // waves / threads of this width's workgroup
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int HA0 = T.ha_sz, HR0 = T.hr_sz;
-    float* const act = smem;
-    float* const hs = act + kTileM * LD;      // then rowinfo | gdir | red | comp: CFN_PHASE_LOCALS
-
-    const int tid = threadIdx.x, lane = lane_id(), wave0 = wave_id();
-    const float* const wp0 = A.wp;
-    const __bf16* const wp160 = reinterpret_cast<const __bf16*>(A.wp16);
-    const int S0 = A.S, K0 = A.K;
-    const int ic0 = T.ic, icv0 = T.icv;
-    const int Dn0 = T.D, skip0 = T.skip;
-    const int64_t n_units = (MODE == 0) ? A.N : (A.P + kTileM - 1) / kTileM;
+    constexpr bool kGeom = false;
+    CFN_FWD_KERNEL_LOCALS;
 
     float ent_r_sum = 0.f, ent_a_sum = 0.f;   // per-lane partial sums of the log-det terms (TRAIN)
 
@@ -198,14 +211,8 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
     const float r_std[3] = {A.flat[5], A.flat[6], A.flat[7]};
 
     for (int64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        float ro[3], rd[3], nearv = 0.f, farv = 1.f, dnorm = 0.f;
-        CFN_PHASE_ARGS;
+        CFN_FWD_UNIT_RAY;
         if (MODE == 0) {
-            const float* r = A.rays + unit * 11;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) { ro[d] = r[d]; rd[d] = r[3 + d]; }
-            nearv = r[6]; farv = r[7];
-            dnorm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);   // torch.norm(rays_d) RUN:429
             if (tid < 32) {
                 gdir[tid] = (tid < icv) ? enc_channel(r + 8, tid) : 0.f;
             }
@@ -217,160 +224,9 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
         const int n_chunks = (MODE == 0) ? chunks_per_ray : 1;
         for (int chunk = 0; chunk < n_chunks; ++chunk) {
             CFN_PHASE_ARGS;
-            // global point index of row 0 and number of valid rows of this tile
-            const int64_t p0 = (MODE == 0) ? unit * (int64_t)S + (int64_t)chunk * kTileM : unit * (int64_t)kTileM;
-            const int rows_valid = (MODE == 0) ? min(kTileM, S - chunk * kTileM) : (int)min((int64_t)kTileM, A.P - p0);
-            const int64_t tile_idx = (MODE == 0) ? unit * chunks_per_ray + chunk : unit;
-            constexpr int kMbStride = (W / 32) * 64;        // mask words per (layer, tile)
-
-            // ---- 1. sampling along the ray (RUN:510-534): z for rows 0..64, pts for rows 0..63
-            if (MODE == 0) {
-                const float* const a_zin = A.z_in;
-                const float* const a_tv = A.t_vals;
-                const float* const a_tr = A.t_rand;
-                float* const a_pts = A.pts;
-                float* const a_stz = A.st_z;
-                const int a_flags = A.flags;
-                fetched_together(a_zin, a_tv, a_tr, a_pts, a_stz, a_flags);
-                if (tid <= kTileM) {
-                    const int s = chunk * kTileM + tid;
-                    float zv = 0.f, px = 0.f, py = 0.f, pz = 0.f;
-                    if (s < S) {
-                        // every input of this sample is requested before the first is used (round 4): written as nested conditionals the
-                        // loads sat behind one another, each with its own full wait - four serialised memory round trips at every tile
-                        // start, with 191 of the workgroup's 256 threads waiting at the barrier below.  Same arithmetic.
-                        const int64_t si = unit * (int64_t)S + s;
-                        const float tv0 = a_tv[s], tvp = a_tv[min(s + 1, S - 1)], tvm = a_tv[max(s - 1, 0)];
-                        float trv = 0.f, zin = 0.f;
-                        if (a_tr != nullptr) trv = a_tr[si];
-                        if (a_zin != nullptr) zin = a_zin[si];
-                        if (a_zin != nullptr) {
-                            zv = zin;                                                              // explicit depths (extension)
-                        } else {
-                            const bool lind = (a_flags & CFNERF_F_LINDISP) != 0;
-                            const float zc = zlin_f(tv0, nearv, farv, lind);
-                            zv = zc;
-                            if (a_tr != nullptr) {                                                 // RUN:518-532
-                                const float upper = (s == S - 1) ? zc : 0.5f * (zlin_f(tvp, nearv, farv, lind) + zc);
-                                const float lower = (s == 0) ? zc : 0.5f * (zc + zlin_f(tvm, nearv, farv, lind));
-                                zv = lower + (upper - lower) * trv;
-                            }
-                        }
-                        px = ro[0] + rd[0] * zv; py = ro[1] + rd[1] * zv; pz = ro[2] + rd[2] * zv;  // RUN:534
-                        if (tid < kTileM) {
-                            if (a_pts != nullptr) {
-                                float* o = a_pts + (unit * (int64_t)S + s) * 3;
-                                o[0] = px; o[1] = py; o[2] = pz;
-                            }
-                            if (a_stz != nullptr) a_stz[unit * (int64_t)S + s] = zv;
-                        }
-                    }
-                    float* ri = rowinfo + tid * 4;
-                    ri[0] = px; ri[1] = py; ri[2] = pz; ri[3] = zv;
-                }
-                __syncthreads();
-            }
-            // Biases are fetched ONE PHASE AHEAD of the accumulator initialisation that needs them (the accumulators must
-            // hold them before a layer's first MFMA, so a fetch at the top of the layer is an exposed L2 round trip per layer):
-            // layer 0's rides under the encoding, layer l+1's under layer l's MFMAs, and so on down the heads.
-            float bias_n[C::NTW];
-            // Operand-table entries travel ONE PHASE AHEAD as well (16 bytes = one s_load_dwordx4 each, cfnerf_device.h: kload): a trunk layer
-            // runs on the entry fetched two layers earlier, prefetches the next layer's bias with the entry fetched one layer earlier, and
-            // fetches the one after - so no layer starts by waiting for the constant cache in front of its first weight loads.
-            SubL tl_cur = kload(T.trunk[0]);
-            SubL tl_nxt = kload((1 < Dn) ? T.trunk[1] : T.ft);
-            const SubL tl_skip = kload(T.skipseg);
-            // ... and so do the stash destinations of the layer epilogues: this tile's rows of layer 0 + a per-layer stride, fetched here
-            // (four constant-cache round trips per layer when each field is loaded at its first use behind the epilogue's barrier)
-            float* const te_st0 = (A.st_h != nullptr) ? A.st_h + (size_t)p0 * W : nullptr;
-            uint32_t* const te_mb0 = (A.st_mbits != nullptr) ? A.st_mbits + (size_t)tile_idx * kMbStride : nullptr;
-            const size_t te_st_step = (size_t)A.P * W, te_mb_step = (size_t)A.n_tiles * kMbStride;
-            load_bias<C::NTW>(tl_cur, wave, kWv, wp, bias_n);
-            // ---- 2. positional encoding of the tile into act[:, 0:64)   (HLP:42-51, RUN:70-71)
-            encode_tile<MODE, LD, PREC, kThr>(act, rowinfo, A.x, p0, rows_valid, ic, icv);
-            // gamma(p) is needed again at the skip layer, five layers later, when the in-place tile has long been overwritten.
-            // Re-evaluating it there cost ~800 vector instructions per wave and tile (30 correctly rounded sincosf per point);
-            // instead the tile is parked as 16 KB of row-major fp32 - in the activation stash when there is one (the backward
-            // wants it there anyway), else in this workgroup's slot of a small L2-resident scratch - and fetched back with
-            // four 16-byte loads per thread.
-            // The EVAL variants of the exact-fp32 path keep it in REGISTERS instead (16 per thread with 4 waves, 8 with 8): the scratch
-            // slot was rewritten every tile and every one of those writes went through L2 to memory - 33 MB of WRITE_SIZE per C2
-            // launch against 82 KB of outputs (profiles/r02_traffic.json).  (The split-bf16 eval kernel has no registers to spare and the
-            // train variants want the tile in the stash anyway: they park it in memory as before.)
-            constexpr bool kParkRegs = MODE == 0 && !TRAIN && PREC == PREC_F32;
-            constexpr int kParkN = kTileM * 16 / kThr;
-            f32x4 park[kParkRegs ? kParkN : 1];
-            float* enc_park = (MODE == 0 && !kParkRegs) ? (A.st_enc != nullptr ? A.st_enc + p0 * 64 : A.enc_scratch + (size_t)blockIdx.x * (kTileM * 64)) : nullptr;
-            if (kParkRegs) {
-                __syncthreads();
-#pragma unroll
-                for (int i = 0; i < kParkN; ++i) {
-                    const int idx = tid + i * kThr, row = idx >> 4, q = idx & 15;
-                    park[i] = *reinterpret_cast<const f32x4*>(act + row * LD + 4 * q);
-                }
-            } else if (MODE == 0 || A.st_enc != nullptr) {
-                __syncthreads();
-                float* dst = (MODE == 0) ? enc_park : A.st_enc + p0 * 64;
-                for (int idx = tid; idx < kTileM * 16; idx += kThr) {
-                    const int row = idx >> 4, q = idx & 15;
-                    if (row < rows_valid) {
-                        f32x4 v;
-                        const float* src = act + row * LD;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = act_load<PREC>(src, LD, 4 * q + c);
-                        if (A.st_enc != nullptr) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst + row * 64 + 4 * q));
-                        else *reinterpret_cast<f32x4*>(dst + row * 64 + 4 * q) = v;
-                    }
-                }
-            }
-            __syncthreads();
-            // ---- 3. trunk: D x (Linear + ReLU), skip concat after layer D/2   (MOD:168-172)
-            for (int l = 0; l < Dn; ++l) {
-                CFN_PHASE_ARGS;
-                f32x16 acc[2][C::NTW];
-                const SubL tl_nn = kload((l + 2 < Dn) ? T.trunk[l + 2] : T.ft);                 // (in flight under this layer's MFMAs)
-                acc_init(acc, bias_n);
-                // the accumulators take the bias fetched a layer ago (its wait also drains the previous layer's stash stores: one counter);
-                // only THEN is the next layer's bias requested - hoisted above that wait it would expose an L2 round trip per layer
-                asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[0][C::NTW - 1][0]) : "memory");
-                load_bias<C::NTW>(tl_nxt, wave, kWv, wp, bias_n);                               // next layer's / the feature head's
-                mma_any<C::NTW, PREC, 2>(acc, tl_cur, wave, kWv, wp, wp16, act, LD);
-                // (all four dwords of the prefetched entry stay live to here: the fp32 kernels never read w16_off, and a dead destination
-                // register of an s_load in flight gets reused at once - a write-after-write wait on the load that was meant to be hidden)
-                asm volatile("" :: "s"(tl_nn.w16_off));
-                if (l >= 1 && l - 1 == skip_l) {
-                    __syncthreads();                 // every wave is done reading h_{l-1}
-                    if (kParkRegs) {                 // act[:, 0:64) <- gamma(p) again, from the registers it was kept in
-#pragma unroll
-                        for (int i = 0; i < kParkN; ++i) {
-                            const int idx = tid + i * kThr, row = idx >> 4, q = idx & 15;
-                            *reinterpret_cast<f32x4*>(act + row * LD + 4 * q) = park[i];
-                        }
-                    } else if (MODE == 0) {          // ... or from where the tile was parked
-                        for (int idx = tid; idx < kTileM * 16; idx += kThr) {
-                            const int row = idx >> 4, q = idx & 15;
-                            f32x4 v; v[0] = v[1] = v[2] = v[3] = 0.f;           // rows past a ragged tile: finite filler
-                            // nt load: served by L2, never by this CU's L1 (the scratch slot is rewritten every tile)
-                            if (row < rows_valid) v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(enc_park + row * 64 + 4 * q));
-                            float* dstl = act + row * LD;
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) act_store<PREC>(dstl, LD, 4 * q + c, v[c]);
-                        }
-                    } else {
-                        encode_tile<MODE, LD, PREC, kThr>(act, rowinfo, A.x, p0, rows_valid, ic, icv);
-                    }
-                    __syncthreads();
-                    mma_any<C::NTW, PREC, 2>(acc, tl_skip, wave, kWv, wp, wp16, act, LD);
-                }
-                __syncthreads();
-                float* st = (te_st0 != nullptr) ? te_st0 + (size_t)l * te_st_step : nullptr;
-                uint32_t* mb = (te_mb0 != nullptr) ? te_mb0 + (size_t)l * te_mb_step : nullptr;
-                constexpr bool kRows = TRAIN && PREC == PREC_F32 && kStashFromLds && !Q4;      // stash by rows out of LDS (see stash_rows) ...
-                store_tiles<C::NTW, ACT_RELU, PREC, TRAIN, TRAIN && !kRows, true, Q4>(acc, tl_cur, wave, kWv, wp, act, LD, 0, st, W, rows_valid, mb);      // ... or (Q4) as pieces from the registers
-                __syncthreads();
-                if (kRows && st != nullptr) stash_rows<W, kThr>(act, LD, st, rows_valid);
-                tl_cur = tl_nxt; tl_nxt = tl_nn;
-            }
+            // ---- 1.-3. sampling, encoding, trunk: the text shared with geom_fwd_kernel
+#define CFN_FWD_GEOM 0
+#include "cfnerf_fwd_trunk_body.h"
             const SubL tl_ft = tl_cur;               // after the last layer: the feature head's entry
 
             // ---- 4. heads: h_alpha = A h (MOD:175), feature = F h (MOD:176).  h_alpha is only 1-2 n-tiles wide: its K is
@@ -399,48 +255,8 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
                     mma_ksplit<PREC, 2>(accA, s_ha, wave, kWv, wp, wp16, act, LD);
                     mma_any<C::NTW, PREC, 2>(accF, tl_ft, wave, kWv, wp, wp16, act, LD);
                 }
-                __syncthreads();                     // every wave is done reading h
-                {
-                    const int lo = lane_id_opaque();
-                    float* lp = act + (4 * (lo >> 5)) * LD + 32 * wave + (lo & 31);      // raw fp32 partial of wave w: act[:, 32w..32w+32)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) lp[(i * 32 + (r & 3) + 8 * (r >> 2)) * LD] = accA[i][0][r];
-                }
-                __syncthreads();
-                {
-                    const int ntc = (int)s_ha.nt, nparts = kWv / ntc;
-                    if (kThr % HA == 0) {
-                        // (round 4) every thread owns ONE column (the thread count is a multiple of h_alpha_size: 32, 64, 128): its bias is
-                        // fetched once, in front of the loop.  Element by element - `wp[b_off + c]` inside the loop - the compiler emitted
-                        // global_load, s_waitcnt vmcnt(0), add, ds_write, store per element: a serialised L2 round trip (which also drains the
-                        // previous element's stash store) 8 ... 32 times per tile, plus an integer division by the run-time HA each.
-                        // Same element -> thread map, same order of the partial sums.
-                        const int c = tid % HA, rstep = kThr / HA;
-                        const float bc = wp[s_ha.b_off + c];
-                        const float* pp0 = act + 32 * (c >> 5) + (c & 31);                   // wave w = part * ntc + n-tile
-                        for (int row = tid / HA; row < kTileM; row += rstep) {
-                            const float* pp = pp0 + row * LD;
-                            float v = pp[0];
-                            for (int q = 1; q < nparts; ++q) v += pp[32 * ntc * q];
-                            v += bc;
-                            act_store<PREC>(hs + row * HLD, HLD, c, v);
-                            if (st_ha != nullptr && row < rows_valid) st_stream(st_ha + (p0 + row) * HA + c, v);
-                        }
-                    } else {
-                        for (int idx = tid; idx < kTileM * HA; idx += kThr) {
-                            const int row = idx / HA, c = idx - row * HA;
-                            const float* pp = act + row * LD + 32 * (c >> 5) + (c & 31);
-                            float v = pp[0];
-                            for (int q = 1; q < nparts; ++q) v += pp[32 * ntc * q];
-                            v += wp[s_ha.b_off + c];
-                            act_store<PREC>(hs + row * HLD, HLD, c, v);
-                            if (st_ha != nullptr && row < rows_valid) st_stream(st_ha + (p0 + row) * HA + c, v);
-                        }
-                    }
-                }
-                __syncthreads();
+#include "cfnerf_fwd_halpha_body.h"
+#undef CFN_FWD_GEOM
                 // (Q4 variant: the feature stash has left from the registers above; here the tile only goes to LDS)
                 constexpr bool kRows = TRAIN && PREC == PREC_F32 && kStashFromLds && !Q4;
                 store_tiles<C::NTW, ACT_NONE, PREC, false, TRAIN && !kRows && !Q4, true>(accF, tl_ft, wave, kWv, wp, act, LD, 0,
@@ -777,14 +593,12 @@ void fused_fwd_kernel(const FwdArgs A_, const NetTab T_) {
         }
       }
     }
-#undef CFN_PHASE_ARGS
-#undef CFN_PHASE_LOCALS
-#undef CFN_KARGS
 }
 
 // CFNERF_F_GEOMETRY: columns 2..5 of a ray's [6] statistics row from the ray's final comp[k] = (_ _ _ depth acc T disp _) - the wave-per-quantity
-// part of kstats_ext_epilogue for its columns 8..11, operation for operation (a copy, so that the EXT variants are compiled from what they were):
-// wave 0 the spread of the disparity, 1 of the depth, 2 mean and spread of the accumulated opacity.
+// part of kstats_ext_epilogue for its columns 8..11, operation for operation: wave 0 the spread of the disparity, 1 of the depth, 2 mean and
+// spread of the accumulated opacity.  A copy: with the extended epilogue calling this function, or both including the statements as text, the
+// four EXT variants of a width came out 11 shorter to 6 longer (same floating-point operations), so the copy stays.
 __device__ __forceinline__ void kstats_geom_epilogue(const float* comp, int K, int wave, int lane, float* __restrict__ ks) {
     if (wave >= 3) return;
     const float fK = (float)K;
@@ -804,220 +618,43 @@ __device__ __forceinline__ void kstats_geom_epilogue(const float* comp, int K, i
 // CFNERF_F_GEOMETRY (eval branch): the fused forward with the colour half removed - sampling, encoding, trunk, the h_alpha head, the density
 // flow head, the K density flows and (ray mode) the composite's depth / accumulated-opacity sums.  No feature head, views layer, h_rgb head,
 // colour flow heads or colour flows: 114 560 of the 614 144 MACs per point at W = 256 and three quarters of the flow phase's transcendentals.
-// A kernel of its own (not a variant of fused_fwd_kernel: those are compiled from what they were).  Phases 1-3 and the h_alpha head are the
-// eval variants' calls on the same operands in the same order, the density chain shares no arithmetic with the colour chain and the library is
-// built without fp contraction, so every output is bit for bit the unflagged eval launch's:
+// Shared with fused_fwd_kernel as text: the scaffolding above, phases 1-3 (cfnerf_fwd_trunk_body.h) and the h_alpha head's k-split sum
+// (cfnerf_fwd_halpha_body.h), with TRAIN = Q4 = false - the eval variants' statements on the same operands in the same order.  Its own: the
+// h_alpha head's MFMA without a feature head beside it, the density flow head on wave 0, the density flows + composite (flow_alpha_fwd, not a
+// copy of flows_fwd) and the ray outputs.  The density chain shares no arithmetic with the colour chain and the library is built without fp
+// contraction, so every output is bit for bit the unflagged eval launch's:
 //   MODE 1  raw [P,K] = raw[..., 3] of the full launch;
 //   MODE 0  raw [N,S,K], weights, pts, depth / disp [N,K] as before and kstats [N,6] = columns 6..11 of a CFNERF_F_KSTATS_EXT row.
 template <int W, int MODE /*0 rays, 1 points*/, int PREC>
 __global__ __launch_bounds__(FwdCfg<W>::NTHR, 2)
 void geom_fwd_kernel(const FwdArgs A_, const NetTab T_) {
-#define CFN_PHASE_LOCALS(F)                                                                                                              \
-    [[maybe_unused]] const int HA = F(HA0), HLD = HA + 4, S = F(S0), K = F(K0), ic = F(ic0), icv = F(icv0), wave = F(wave0);               \
-    [[maybe_unused]] const int chunks_per_ray = (S + kTileM - 1) / kTileM, Dn = F(Dn0), skip_l = F(skip0);                                \
-    [[maybe_unused]] float* const rowinfo = hs + kTileM * HLD; /* [65][4]: x y z zval */                                                  \
-    [[maybe_unused]] float* const comp = rowinfo + 68 * 4 + 32 + 16; /* (the layout of fwd_lds_bytes) [comp_rows(K)][8]: _ _ _ depth acc T disp _ */ \
-    [[maybe_unused]] const float* __restrict__ const wp = F(wp0);                                                                          \
-    [[maybe_unused]] const __bf16* __restrict__ const wp16 = F(wp160)
-    (void)A_; (void)T_;
-#define CFN_KARGS const CFN_KCONST FwdKargs* kq_ = kernarg_fresh<FwdKargs>(); const CFN_KCONST FwdArgs& A = kq_->A; const CFN_KCONST NetTab& T = kq_->T
-#define CFN_PHASE_ARGS CFN_KARGS; CFN_PHASE_LOCALS(sgpr_fresh)
-    CFN_KARGS;
-    using C = FwdCfg<W>;
-    constexpr int LD = C::LD;
-    constexpr int kWv = C::NWV, kThr = C::NTHR;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int HA0 = T.ha_sz;
-    float* const act = smem;
-    float* const hs = act + kTileM * LD;
-
-    const int tid = threadIdx.x, lane = lane_id(), wave0 = wave_id();
-    const float* const wp0 = A.wp;
-    const __bf16* const wp160 = reinterpret_cast<const __bf16*>(A.wp16);
-    const int S0 = A.S, K0 = A.K;
-    const int ic0 = T.ic, icv0 = T.icv;
-    const int Dn0 = T.D, skip0 = T.skip;
-    const int64_t n_units = (MODE == 0) ? A.N : (A.P + kTileM - 1) / kTileM;
+    constexpr bool kGeom = true, TRAIN = false, Q4 = false;          // the constants the shared text branches on: eval only, no stash
+    CFN_FWD_KERNEL_LOCALS;
     const float a_mean = A.flat[0], a_std = A.flat[1];
 
     for (int64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        float ro[3], rd[3], nearv = 0.f, farv = 1.f, dnorm = 0.f;
-        CFN_PHASE_ARGS;
-        if (MODE == 0) {
-            const float* r = A.rays + unit * 11;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) { ro[d] = r[d]; rd[d] = r[3 + d]; }
-            nearv = r[6]; farv = r[7];
-            dnorm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);   // torch.norm(rays_d) RUN:429
-            if (tid < K) {
-                float* c = comp + tid * 8;
-                c[3] = c[4] = 0.f; c[5] = 1.f;
-            }
+        CFN_FWD_UNIT_RAY;
+        if (MODE == 0 && tid < K) {
+            float* c = comp + tid * 8;
+            c[3] = c[4] = 0.f; c[5] = 1.f;
         }
         const int n_chunks = (MODE == 0) ? chunks_per_ray : 1;
         for (int chunk = 0; chunk < n_chunks; ++chunk) {
             CFN_PHASE_ARGS;
-            const int64_t p0 = (MODE == 0) ? unit * (int64_t)S + (int64_t)chunk * kTileM : unit * (int64_t)kTileM;
-            const int rows_valid = (MODE == 0) ? min(kTileM, S - chunk * kTileM) : (int)min((int64_t)kTileM, A.P - p0);
-
-            // ---- 1. sampling along the ray (RUN:510-534), as in fused_fwd_kernel
-            if (MODE == 0) {
-                const float* const a_zin = A.z_in;
-                const float* const a_tv = A.t_vals;
-                const float* const a_tr = A.t_rand;
-                float* const a_pts = A.pts;
-                const int a_flags = A.flags;
-                fetched_together(a_zin, a_tv, a_tr, a_pts, a_flags);
-                if (tid <= kTileM) {
-                    const int s = chunk * kTileM + tid;
-                    float zv = 0.f, px = 0.f, py = 0.f, pz = 0.f;
-                    if (s < S) {
-                        const int64_t si = unit * (int64_t)S + s;
-                        // explicit depths: the sample table is NOT read (it may be NULL or shorter than S, include/cfnerf.h) - the condition is
-                        // wave-uniform and taken once around the three loads, which still leave together in front of one wait
-                        float tv0 = 0.f, tvp = 0.f, tvm = 0.f;
-                        if (a_zin == nullptr) { tv0 = a_tv[s]; tvp = a_tv[min(s + 1, S - 1)]; tvm = a_tv[max(s - 1, 0)]; }
-                        float trv = 0.f, zin = 0.f;
-                        if (a_tr != nullptr) trv = a_tr[si];
-                        if (a_zin != nullptr) zin = a_zin[si];
-                        if (a_zin != nullptr) {
-                            zv = zin;
-                        } else {
-                            const bool lind = (a_flags & CFNERF_F_LINDISP) != 0;
-                            const float zc = zlin_f(tv0, nearv, farv, lind);
-                            zv = zc;
-                            if (a_tr != nullptr) {                                                 // RUN:518-532
-                                const float upper = (s == S - 1) ? zc : 0.5f * (zlin_f(tvp, nearv, farv, lind) + zc);
-                                const float lower = (s == 0) ? zc : 0.5f * (zc + zlin_f(tvm, nearv, farv, lind));
-                                zv = lower + (upper - lower) * trv;
-                            }
-                        }
-                        px = ro[0] + rd[0] * zv; py = ro[1] + rd[1] * zv; pz = ro[2] + rd[2] * zv;  // RUN:534
-                        if (tid < kTileM && a_pts != nullptr) {
-                            float* o = a_pts + (unit * (int64_t)S + s) * 3;
-                            o[0] = px; o[1] = py; o[2] = pz;
-                        }
-                    }
-                    float* ri = rowinfo + tid * 4;
-                    ri[0] = px; ri[1] = py; ri[2] = pz; ri[3] = zv;
-                }
-                __syncthreads();
-            }
-            // biases and operand-table entries travel one phase ahead, as in fused_fwd_kernel; behind the last trunk layer comes the h_alpha head
-            float bias_n[C::NTW];
-            SubL tl_cur = kload(T.trunk[0]);
-            SubL tl_nxt = kload((1 < Dn) ? T.trunk[1] : T.ha);
-            const SubL tl_skip = kload(T.skipseg);
-            load_bias<C::NTW>(tl_cur, wave, kWv, wp, bias_n);
-            // ---- 2. positional encoding of the tile into act[:, 0:64) and its parking for the skip layer (registers / the scratch slot)
-            encode_tile<MODE, LD, PREC, kThr>(act, rowinfo, A.x, p0, rows_valid, ic, icv);
-            constexpr bool kParkRegs = MODE == 0 && PREC == PREC_F32;
-            constexpr int kParkN = kTileM * 16 / kThr;
-            f32x4 park[kParkRegs ? kParkN : 1];
-            float* enc_park = (MODE == 0 && !kParkRegs) ? A.enc_scratch + (size_t)blockIdx.x * (kTileM * 64) : nullptr;
-            if (kParkRegs) {
-                __syncthreads();
-#pragma unroll
-                for (int i = 0; i < kParkN; ++i) {
-                    const int idx = tid + i * kThr, row = idx >> 4, q = idx & 15;
-                    park[i] = *reinterpret_cast<const f32x4*>(act + row * LD + 4 * q);
-                }
-            } else if (MODE == 0) {
-                __syncthreads();
-                for (int idx = tid; idx < kTileM * 16; idx += kThr) {
-                    const int row = idx >> 4, q = idx & 15;
-                    if (row < rows_valid) {
-                        f32x4 v;
-                        const float* src = act + row * LD;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = act_load<PREC>(src, LD, 4 * q + c);
-                        *reinterpret_cast<f32x4*>(enc_park + row * 64 + 4 * q) = v;
-                    }
-                }
-            }
-            __syncthreads();
-            // ---- 3. trunk: D x (Linear + ReLU), skip concat after layer D/2   (MOD:168-172)
-            for (int l = 0; l < Dn; ++l) {
-                CFN_PHASE_ARGS;
-                f32x16 acc[2][C::NTW];
-                const SubL tl_nn = kload((l + 2 < Dn) ? T.trunk[l + 2] : T.ha);
-                acc_init(acc, bias_n);
-                asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[0][C::NTW - 1][0]) : "memory");
-                if (l + 1 < Dn) load_bias<C::NTW>(tl_nxt, wave, kWv, wp, bias_n);                  // (the h_alpha head adds its bias after the k-split sum)
-                mma_any<C::NTW, PREC, 2>(acc, tl_cur, wave, kWv, wp, wp16, act, LD);
-                asm volatile("" :: "s"(tl_nn.w16_off));
-                if (l >= 1 && l - 1 == skip_l) {
-                    __syncthreads();                 // every wave is done reading h_{l-1}
-                    if (kParkRegs) {
-#pragma unroll
-                        for (int i = 0; i < kParkN; ++i) {
-                            const int idx = tid + i * kThr, row = idx >> 4, q = idx & 15;
-                            *reinterpret_cast<f32x4*>(act + row * LD + 4 * q) = park[i];
-                        }
-                    } else if (MODE == 0) {
-                        for (int idx = tid; idx < kTileM * 16; idx += kThr) {
-                            const int row = idx >> 4, q = idx & 15;
-                            f32x4 v; v[0] = v[1] = v[2] = v[3] = 0.f;           // rows past a ragged tile: finite filler
-                            if (row < rows_valid) v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(enc_park + row * 64 + 4 * q));
-                            float* dstl = act + row * LD;
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) act_store<PREC>(dstl, LD, 4 * q + c, v[c]);
-                        }
-                    } else {
-                        encode_tile<MODE, LD, PREC, kThr>(act, rowinfo, A.x, p0, rows_valid, ic, icv);
-                    }
-                    __syncthreads();
-                    mma_any<C::NTW, PREC, 2>(acc, tl_skip, wave, kWv, wp, wp16, act, LD);
-                }
-                __syncthreads();
-                store_tiles<C::NTW, ACT_RELU, PREC, false, false, true>(acc, tl_cur, wave, kWv, wp, act, LD, 0, nullptr, W, rows_valid);
-                __syncthreads();
-                tl_cur = tl_nxt; tl_nxt = tl_nn;
-            }
+            // ---- 1.-3. sampling, encoding, trunk: the text shared with fused_fwd_kernel
+#define CFN_FWD_GEOM 1
+#include "cfnerf_fwd_trunk_body.h"
             const SubL s_ha = tl_cur;                // after the last layer: the h_alpha head's entry
 
-            // ---- 4. the h_alpha head alone (MOD:175): K split over the waves, the partial tiles summed through act[] in the order of
-            //         fused_fwd_kernel (pp[0], q = 1 .. nparts-1, the bias) into hs
+            // ---- 4. the h_alpha head alone (MOD:175): K split over the waves, then the shared partial sum into hs
             {
                 CFN_PHASE_ARGS;
                 f32x16 accA[2][1];
+                float* const st_ha = nullptr;        // (no stash)
                 acc_zero(accA);
                 mma_ksplit<PREC, 2>(accA, s_ha, wave, kWv, wp, wp16, act, LD);
-                __syncthreads();                     // every wave is done reading h
-                {
-                    const int lo = lane_id_opaque();
-                    float* lp = act + (4 * (lo >> 5)) * LD + 32 * wave + (lo & 31);      // raw fp32 partial of wave w: act[:, 32w..32w+32)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) lp[(i * 32 + (r & 3) + 8 * (r >> 2)) * LD] = accA[i][0][r];
-                }
-                __syncthreads();
-                {
-                    const int ntc = (int)s_ha.nt, nparts = kWv / ntc;
-                    if (kThr % HA == 0) {
-                        const int c = tid % HA, rstep = kThr / HA;
-                        const float bc = wp[s_ha.b_off + c];
-                        const float* pp0 = act + 32 * (c >> 5) + (c & 31);                   // wave w = part * ntc + n-tile
-                        for (int row = tid / HA; row < kTileM; row += rstep) {
-                            const float* pp = pp0 + row * LD;
-                            float v = pp[0];
-                            for (int q = 1; q < nparts; ++q) v += pp[32 * ntc * q];
-                            v += bc;
-                            act_store<PREC>(hs + row * HLD, HLD, c, v);
-                        }
-                    } else {
-                        for (int idx = tid; idx < kTileM * HA; idx += kThr) {
-                            const int row = idx / HA, c = idx - row * HA;
-                            const float* pp = act + row * LD + 32 * (c >> 5) + (c & 31);
-                            float v = pp[0];
-                            for (int q = 1; q < nparts; ++q) v += pp[32 * ntc * q];
-                            v += wp[s_ha.b_off + c];
-                            act_store<PREC>(hs + row * HLD, HLD, c, v);
-                        }
-                    }
-                }
-                __syncthreads();
+#include "cfnerf_fwd_halpha_body.h"
+#undef CFN_FWD_GEOM
             }
             // ---- 7. the density flow head (MOD:366-383), once per point, on wave 0: theta_alpha -> act[:, kThetaRgb : kThetaRgb + 32)
             {
@@ -1174,10 +811,12 @@ void geom_fwd_kernel(const FwdArgs A_, const NetTab T_) {
         }
         __syncthreads();
     }  // units
+}
+#undef CFN_FWD_UNIT_RAY
+#undef CFN_FWD_KERNEL_LOCALS
 #undef CFN_PHASE_ARGS
 #undef CFN_PHASE_LOCALS
 #undef CFN_KARGS
-}
 
 // base-Gaussian log-densities of one [K,4] set of latents, summed over k (MOD:268,283: Normal(mean, std).log_prob of z0 = eps std + mean)
 __device__ __forceinline__ void base_logprob_sums(const float* eps, int K, const float* flat, float& base_a, float& base_r) {
@@ -1368,17 +1007,7 @@ void sample_points_kernel(const float* __restrict__ rays, const float* __restric
         for (int ch = 0; ch < nch; ++ch) {
             const int s = ch * 64 + lane;
             const bool valid = s < S;
-            // every operand requested before the first is used (clamped neighbours: the selects below take what rounds 1-3 computed)
-            const int sc = min(s, S - 1);
-            const float tc = t_vals[sc], tp = t_vals[min(sc + 1, S - 1)], tm = t_vals[max(sc - 1, 0)];
-            const float tr = (t_rand != nullptr) ? t_rand[n * S + sc] : 0.f;
-            const float zc = zlin_f(tc, nearv, farv, lind);
-            float zv = zc;
-            if (t_rand != nullptr) {
-                const float upper = (sc == S - 1) ? zc : 0.5f * (zlin_f(tp, nearv, farv, lind) + zc);
-                const float lower = (sc == 0) ? zc : 0.5f * (zc + zlin_f(tm, nearv, farv, lind));
-                zv = lower + (upper - lower) * tr;
-            }
+            const float zv = strat_depth(t_vals, t_rand, n, S, min(s, S - 1), nearv, farv, lind);      // (lanes past S: the last sample's again)
             if (valid) z_out[n * S + s] = zv;
             if (pts != nullptr) {
                 wave_lds_turn();
@@ -1432,7 +1061,7 @@ void sample_pdf_kernel(const float* __restrict__ rays, const float* __restrict__
         for (int s = lane; s < S; s += 64) {
             const float zc = zlin_f(t_vals[s], nearv, farv, lind);
             float zv = zc;
-            if (t_rand != nullptr) {
+            if (t_rand != nullptr) {      // strat_jitter (cfnerf_device.h) with each neighbour's table entry loaded under its own condition: as a call the kernel grew
                 const float upper = (s == S - 1) ? zc : 0.5f * (zlin_f(t_vals[s + 1], nearv, farv, lind) + zc);
                 const float lower = (s == 0) ? zc : 0.5f * (zc + zlin_f(t_vals[s - 1], nearv, farv, lind));
                 zv = lower + (upper - lower) * t_rand[n * (int64_t)S + s];
@@ -1540,40 +1169,11 @@ static int max_blocks_per_cu(const void* fn, size_t lds, int threads) {
     return nb;
 }
 
-template <int W, int MODE, bool TRAIN, int PREC, bool Q4 = false>
-static hipError_t launch_fwd_t(const FwdArgs& a, const NetTab& ht, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
-    auto fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4>;
-    if constexpr (TRAIN)
-        if (a.flags & CFNERF_F_EPS_ROWS) fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4, true>;      // one latent row per ray / point
-    if constexpr (MODE == 0 && !Q4)
-        if (a.flags & CFNERF_F_KSTATS_EXT) fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, false, false, true>;      // kstats [N,12], sqerr [N,6] (the ABI refuses it with a stash or rows)
-    const size_t lds = fwd_lds_bytes(W, ht.ha_sz, a.K);
-    const int64_t units = (MODE == 0) ? a.N : (a.P + kTileM - 1) / kTileM;
-    int grid = (int)std::min<int64_t>(units, (int64_t)n_cu * per_cu);
-    if (grid < 1) grid = 1;
-    if (grid_out) *grid_out = grid;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(FwdCfg<W>::NTHR), lds, st, a, ht);
-    return hipGetLastError();
-}
-
+// One launch of a forward kernel of width W, full or geometry-only (same signature, LDS tile and launch bounds): a workgroup per unit - ray or
+// 64-point tile - up to the occupancy read by fwd_attrs_w, the units beyond that walked by the kernel's loop.
+using FwdKernel = void (*)(const FwdArgs, const NetTab);
 template <int W>
-static hipError_t launch_fwd_w(const FwdArgs& a, const NetTab& ht, int mode, bool train, int prec, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
-    if (prec == PREC_BF16X3) {
-        if (mode == 0) return train ? launch_fwd_t<W, 0, true, PREC_BF16X3>(a, ht, n_cu, per_cu, st, grid_out) : launch_fwd_t<W, 0, false, PREC_BF16X3>(a, ht, n_cu, per_cu, st, grid_out);
-        return train ? launch_fwd_t<W, 1, true, PREC_BF16X3>(a, ht, n_cu, per_cu, st, grid_out) : launch_fwd_t<W, 1, false, PREC_BF16X3>(a, ht, n_cu, per_cu, st, grid_out);
-    }
-    if (train && a.q4)            // whole tiles + a stash in fp32 mode: the variant that writes the wide streams as Q4 pieces
-        return mode == 0 ? launch_fwd_t<W, 0, true, PREC_F32, true>(a, ht, n_cu, per_cu, st, grid_out) : launch_fwd_t<W, 1, true, PREC_F32, true>(a, ht, n_cu, per_cu, st, grid_out);
-    if (mode == 0) return train ? launch_fwd_t<W, 0, true, PREC_F32>(a, ht, n_cu, per_cu, st, grid_out) : launch_fwd_t<W, 0, false, PREC_F32>(a, ht, n_cu, per_cu, st, grid_out);
-    return train ? launch_fwd_t<W, 1, true, PREC_F32>(a, ht, n_cu, per_cu, st, grid_out) : launch_fwd_t<W, 1, false, PREC_F32>(a, ht, n_cu, per_cu, st, grid_out);
-}
-
-// CFNERF_F_GEOMETRY: the geometry-only kernel of (width, mode, precision); the ABI admits the flag on the eval branch only
-template <int W>
-static hipError_t launch_geom_w(const FwdArgs& a, const NetTab& ht, int mode, int prec, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
-    auto fn = geom_fwd_kernel<W, 0, PREC_F32>;
-    if (prec == PREC_BF16X3) fn = mode == 0 ? geom_fwd_kernel<W, 0, PREC_BF16X3> : geom_fwd_kernel<W, 1, PREC_BF16X3>;
-    else if (mode != 0) fn = geom_fwd_kernel<W, 1, PREC_F32>;
+static hipError_t launch_fwd_fn(FwdKernel fn, const FwdArgs& a, const NetTab& ht, int mode, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
     const size_t lds = fwd_lds_bytes(W, ht.ha_sz, a.K);
     const int64_t units = (mode == 0) ? a.N : (a.P + kTileM - 1) / kTileM;
     int grid = (int)std::min<int64_t>(units, (int64_t)n_cu * per_cu);
@@ -1583,18 +1183,37 @@ static hipError_t launch_geom_w(const FwdArgs& a, const NetTab& ht, int mode, in
     return hipGetLastError();
 }
 
-hipError_t launch_fused_fwd(const FwdArgs& a, const NetTab& ht, int mode, bool train, int prec, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
-    if (a.flags & CFNERF_F_GEOMETRY) {
-        if (train) return hipErrorInvalidValue;
-        switch (ht.W) {
-#define CFN_W_CASE(w) case w: return launch_geom_w<w>(a, ht, mode, prec, n_cu, per_cu, st, grid_out);
-            CFN_FOR_EACH_WIDTH(CFN_W_CASE)
-#undef CFN_W_CASE
-        }
-        return hipErrorInvalidValue;
+// the full kernel of (mode, branch, precision, stash layout) and, by the launch's flags, its latent-rows or extended-statistics variant
+template <int W, int MODE, bool TRAIN, int PREC, bool Q4 = false>
+static FwdKernel fwd_variant(const FwdArgs& a) {
+    FwdKernel fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4>;
+    if constexpr (TRAIN)
+        if (a.flags & CFNERF_F_EPS_ROWS) fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, Q4, true>;      // one latent row per ray / point
+    if constexpr (MODE == 0 && !Q4)
+        if (a.flags & CFNERF_F_KSTATS_EXT) fn = fused_fwd_kernel<W, MODE, TRAIN, PREC, false, false, true>;      // kstats [N,12], sqerr [N,6] (the ABI refuses it with a stash or rows)
+    return fn;
+}
+
+template <int W>
+static FwdKernel fwd_kernel_w(const FwdArgs& a, int mode, bool train, int prec) {
+    if (a.flags & CFNERF_F_GEOMETRY) {       // the geometry-only kernel of (mode, precision); the ABI admits the flag on the eval branch only
+        if (prec == PREC_BF16X3) return mode == 0 ? geom_fwd_kernel<W, 0, PREC_BF16X3> : geom_fwd_kernel<W, 1, PREC_BF16X3>;
+        return mode == 0 ? geom_fwd_kernel<W, 0, PREC_F32> : geom_fwd_kernel<W, 1, PREC_F32>;
     }
+    if (prec == PREC_BF16X3) {
+        if (mode == 0) return train ? fwd_variant<W, 0, true, PREC_BF16X3>(a) : fwd_variant<W, 0, false, PREC_BF16X3>(a);
+        return train ? fwd_variant<W, 1, true, PREC_BF16X3>(a) : fwd_variant<W, 1, false, PREC_BF16X3>(a);
+    }
+    if (train && a.q4)            // whole tiles + a stash in fp32 mode: the variant that writes the wide streams as Q4 pieces
+        return mode == 0 ? fwd_variant<W, 0, true, PREC_F32, true>(a) : fwd_variant<W, 1, true, PREC_F32, true>(a);
+    if (mode == 0) return train ? fwd_variant<W, 0, true, PREC_F32>(a) : fwd_variant<W, 0, false, PREC_F32>(a);
+    return train ? fwd_variant<W, 1, true, PREC_F32>(a) : fwd_variant<W, 1, false, PREC_F32>(a);
+}
+
+hipError_t launch_fused_fwd(const FwdArgs& a, const NetTab& ht, int mode, bool train, int prec, int n_cu, int per_cu, hipStream_t st, int* grid_out) {
+    if ((a.flags & CFNERF_F_GEOMETRY) && train) return hipErrorInvalidValue;
     switch (ht.W) {
-#define CFN_W_CASE(w) case w: return launch_fwd_w<w>(a, ht, mode, train, prec, n_cu, per_cu, st, grid_out);
+#define CFN_W_CASE(w) case w: return launch_fwd_fn<w>(fwd_kernel_w<w>(a, mode, train, prec), a, ht, mode, n_cu, per_cu, st, grid_out);
         CFN_FOR_EACH_WIDTH(CFN_W_CASE)
 #undef CFN_W_CASE
     }
@@ -1606,7 +1225,8 @@ hipError_t launch_fused_fwd(const FwdArgs& a, const NetTab& ht, int mode, bool t
 template <int W>
 static hipError_t fwd_attrs_w(int ha, int* per_cu_out) {
     const size_t lds = fwd_lds_bytes(W, ha, kMaxK);      // the limit; a launch asks for what its K needs
-    const void* fns[20] = {
+    constexpr int kFull = 20;                              // the occupancy is the minimum over the full kernels; the geometry-only ones come last
+    const void* fns[kFull + 4] = {
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32, true>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_F32>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32>),
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, false, PREC_F32>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_F32>),
@@ -1618,20 +1238,15 @@ static hipError_t fwd_attrs_w(int ha, int* per_cu_out) {
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 1, true, PREC_BF16X3, false, true>),
         // the extended-K-statistics variants (CFNERF_F_KSTATS_EXT)
         reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_F32, false, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_F32, false, false, true>),
-        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_BF16X3, false, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3, false, false, true>)};
-    int per_cu = 2;
-    for (const void* fn : fns) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        per_cu = std::min(per_cu, max_blocks_per_cu(fn, fwd_lds_bytes(W, ha, 16), FwdCfg<W>::NTHR));
-    }
-    // the geometry-only kernels (CFNERF_F_GEOMETRY): the same LDS tile and launch bounds, launched with the occupancy read above
-    const void* gfns[4] = {
+        reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, false, PREC_BF16X3, false, false, true>), reinterpret_cast<const void*>(fused_fwd_kernel<W, 0, true, PREC_BF16X3, false, false, true>),
+        // the geometry-only kernels (CFNERF_F_GEOMETRY): the same LDS tile and launch bounds, launched with the occupancy of the full ones
         reinterpret_cast<const void*>(geom_fwd_kernel<W, 0, PREC_F32>), reinterpret_cast<const void*>(geom_fwd_kernel<W, 1, PREC_F32>),
         reinterpret_cast<const void*>(geom_fwd_kernel<W, 0, PREC_BF16X3>), reinterpret_cast<const void*>(geom_fwd_kernel<W, 1, PREC_BF16X3>)};
-    for (const void* fn : gfns) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    int per_cu = 2;
+    for (int i = 0; i < kFull + 4; ++i) {
+        hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
+        if (i < kFull) per_cu = std::min(per_cu, max_blocks_per_cu(fns[i], fwd_lds_bytes(W, ha, 16), FwdCfg<W>::NTHR));
     }
     *per_cu_out = std::max(1, per_cu);
     return hipSuccess;
