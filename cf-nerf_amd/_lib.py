@@ -12,6 +12,9 @@ F_RAY_GRAD = 256
 F_COTANGENTS = 512
 F_SEAM_GRAD = 1024          # goes into the white_bkgd argument of cfnerf_composite_bwd, not into a flags argument
 F_CULL = 0x800              # cfnerf_sample_points: pts is a Cull; cfnerf_composite_fwd: or-ed into white_bkgd, weights_opt is a SparseRaw
+# CFNERF_F_EPS_GRAD (cfnerf_render_fwd / cfnerf_network_fwd with F_STASH: the backward also writes d_eps and d_eps_rows, eps_grad_offsets).  Not an
+# ``F_`` name: tests/test_cull_cpu.py pins how many of those this module has
+FLAG_EPS_GRAD = 0x1000
 
 
 def input_grad_offset(n_params: int) -> int:
@@ -25,6 +28,15 @@ def ray_grad_offsets(n_params: int, N: int, S: int):
     r_off = (n_params + 63) // 64 * 64
     z_off = r_off + (N * 11 + 63) // 64 * 64
     return r_off, z_off, z_off + N * S
+
+
+def eps_grad_offsets(base_end: int, n: int, K: int):
+    """(e_off, er_off, total) of include/cfnerf.h (CFNERF_F_EPS_GRAD), in floats: d_eps [K,4] starts at e_off and d_eps_rows [n,K,4] at er_off
+    of the backward's grad_flat, which then holds ``total`` floats.  ``base_end``: the end of the blocks the stash already asks for -
+    ``n_params``, ``ray_grad_offsets(...)[2]`` with F_RAY_GRAD, ``input_grad_offset(n_params) + P * C`` with F_INPUT_GRAD; ``n``: rays or points"""
+    e_off = (base_end + 63) // 64 * 64
+    er_off = e_off + (4 * K + 63) // 64 * 64
+    return e_off, er_off, er_off + n * K * 4
 
 
 class Cfg(C.Structure):

@@ -660,7 +660,8 @@ class NeRF_Flows(nn.Module):
         LT.check_rows(eps, P, "points", hint=": in netchunk mode render_rays hands one latent row per point of the whole batch, so a custom "
                                              "network_query_fn must evaluate all of them in one NeRF_Flows call")
         want_x = torch.is_grad_enabled() and x.requires_grad
-        if ((torch.is_grad_enabled() and self.flat.requires_grad and not is_test) or want_x) and P > 0:
+        want_eps = torch.is_grad_enabled() and eps.requires_grad      # explicit latents that ask for a gradient (CFNERF_F_EPS_GRAD), either branch
+        if ((torch.is_grad_enabled() and self.flat.requires_grad and not is_test) or want_x or want_eps) and P > 0:
             # the reference's forward is an autograd graph (MOD:188-291): so is this one - cfnerf_network_fwd with the
             # activation stash, differentiated by cfnerf_network_bwd.  Gradients reach the parameters and - when x asks for
             # one (CFNERF_F_INPUT_GRAD: a frozen network still gives x.grad) - the inputs.  The eval branch is a graph in the
@@ -772,9 +773,10 @@ class _NetworkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, model, xf, eps):
-        # xf asks for a gradient: the stash remembers CFNERF_F_INPUT_GRAD and the backward also writes d_x behind the parameter gradient
-        ctx.extra = L.F_INPUT_GRAD if ctx.needs_input_grad[2] else 0
-        xf = _f32c(xf)
+        # xf asks for a gradient: the stash remembers CFNERF_F_INPUT_GRAD and the backward also writes d_x behind the parameter gradient;
+        # the latents ask for one: CFNERF_F_EPS_GRAD, d_eps / d_eps_rows behind that (a frozen network still gives either)
+        ctx.extra = (L.F_INPUT_GRAD if ctx.needs_input_grad[2] else 0) | (L.FLAG_EPS_GRAD if ctx.needs_input_grad[3] else 0)
+        xf, eps = _f32c(xf), _f32c(eps)
         raw, ent = _NetworkFn._forward_stash(model, xf, eps, ctx.extra)
         ctx.model, ctx.xf, ctx.eps, ctx.n_params = model, xf, eps, flat.numel()
         _mark_forward(ctx, model)
@@ -793,8 +795,19 @@ class _NetworkFn(torch.autograd.Function):
             ctx.generation = lib.cfnerf_model_stash_generation(model.handle)
         dr = _f32c(d_raw) if d_raw is not None else None
         de = _f32c(d_ent.reshape(1)) if d_ent is not None else None
+        want_x, want_eps = bool(ctx.extra & L.F_INPUT_GRAD), bool(ctx.extra & L.FLAG_EPS_GRAD)
         if dr is None and de is None:
-            return torch.zeros(ctx.n_params, device=model.flat.device), None, (torch.zeros_like(ctx.xf) if ctx.extra else None), None
+            return (torch.zeros(ctx.n_params, device=model.flat.device), None, (torch.zeros_like(ctx.xf) if want_x else None),
+                    (torch.zeros_like(ctx.eps) if want_eps else None))
+        if want_eps:
+            # CFNERF_F_EPS_GRAD layout of grad_flat (cfnerf.h): d_eps [K,4] from e_off and d_eps_rows [P,K,4] from er_off, behind the blocks of before
+            (P, Cx), K = ctx.xf.shape, ctx.eps.shape[-2]
+            x_off = L.input_grad_offset(ctx.n_params)
+            e_off, er_off, total = L.eps_grad_offsets(x_off + P * Cx if want_x else ctx.n_params, P, K)
+            grad = torch.empty(total, device=model.flat.device)
+            L.check(lib.cfnerf_network_bwd(model.handle, ctx.generation, L.ptr(dr), L.ptr(de), L.ptr(grad), L.stream()), "cfnerf_network_bwd")
+            d_eps = grad[er_off:].view(P, K, 4) if ctx.eps.dim() == 3 else grad[e_off:e_off + K * 4].view(K, 4)
+            return grad[:ctx.n_params], None, (grad[x_off:x_off + P * Cx].view(P, Cx) if want_x else None), d_eps
         if not ctx.extra:
             grad = torch.empty(ctx.n_params, device=model.flat.device)
             L.check(lib.cfnerf_network_bwd(model.handle, ctx.generation, L.ptr(dr), L.ptr(de), L.ptr(grad), L.stream()), "cfnerf_network_bwd")
@@ -996,7 +1009,10 @@ class _RenderFn(torch.autograd.Function):
         ctx.want_rays, ctx.want_z = ctx.needs_input_grad[2], z_vals is not None and ctx.needs_input_grad[8]
         if ctx.want_rays or ctx.want_z:
             flags |= L.F_RAY_GRAD
-        rays = _f32c(rays)
+        ctx.want_eps = ctx.needs_input_grad[5]      # the latents ask for a gradient: CFNERF_F_EPS_GRAD, d_eps / d_eps_rows behind the other blocks
+        if ctx.want_eps:
+            flags |= L.FLAG_EPS_GRAD
+        rays, eps = _f32c(rays), _f32c(eps)
         z_vals = None if z_vals is None else _f32c(z_vals)
         S = z_vals.shape[1] if z_vals is not None else t_vals.shape[0]
         model.ensure_workspace(N, S, K)
@@ -1022,6 +1038,9 @@ class _RenderFn(torch.autograd.Function):
         # CFNERF_F_RAY_GRAD layout of grad_flat (cfnerf.h): the parameter gradient, then d_rays [N,11] from r_off and d_z [N,S] from z_off
         (N, S), n = ctx.NS, ctx.n_params
         r_off, z_off, total = L.ray_grad_offsets(n, N, S) if ray_grad else (n, n, n)
+        K = ctx.shape[2]
+        # CFNERF_F_EPS_GRAD: then d_eps [K,4] from e_off and d_eps_rows [N,K,4] from er_off
+        e_off, er_off, total = L.eps_grad_offsets(total, N, K) if ctx.want_eps else (total, total, total)
         grad = torch.empty(total, device=dev)
         d_rgb = _f32c(d_rgb) if d_rgb is not None else torch.zeros(ctx.shape, device=dev)
         dd = _f32c(d_depth) if d_depth is not None else None
@@ -1034,7 +1053,10 @@ class _RenderFn(torch.autograd.Function):
                 "cfnerf_render_bwd")
         d_rays = grad[r_off:r_off + N * 11].view(N, 11) if ctx.want_rays else None
         d_z = grad[z_off:z_off + N * S].view(N, S) if ctx.want_z else None
-        return (grad[:n] if ctx.needs_input_grad[0] else None), None, d_rays, None, None, None, None, None, d_z, None
+        d_eps = None
+        if ctx.want_eps:        # one set: its gradient; rows: one row per ray
+            d_eps = grad[er_off:er_off + N * K * 4].view(N, K, 4) if ctx.eps.dim() == 3 else grad[e_off:e_off + K * 4].view(K, 4)
+        return (grad[:n] if ctx.needs_input_grad[0] else None), None, d_rays, None, None, d_eps, None, None, d_z, None
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, uniformsample, retraw=False,
@@ -1079,6 +1101,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
     # the reference's render_rays is an autograd graph in the rays too (pose refinement, registration): the fused node differentiates it
     want_rays = torch.is_grad_enabled() and ray_batch.requires_grad
     explicit = LT.pack(eps_alpha, eps_rgb)
+    # ... and in its latents (eps.mul(std).add_(mean), MOD:239,251): explicit ones that ask for a gradient get it, CFNERF_F_EPS_GRAD
+    want_eps = torch.is_grad_enabled() and explicit is not None and explicit.requires_grad
     if is_train:
         # latents.train_latents: the mode's draws in the reference's order (a t_rand of the CPU generator included, unless there is one)
         tr, eps, _ = LT.train_latents(model.latent_draws, explicit, N=N, S=S, K=K, netchunk=model.netchunk, chunk=chunk, perturb=perturb,
@@ -1100,11 +1124,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, is_train, un
         # the reference's graph runs from ray_batch to the loss whatever the query function is: rays that ask for a gradient stay on it
         return _render_rays_unfused(ray_batch.to(torch.float32) if want_rays else rays, model, network_fn, network_query_fn, t_vals, t_rand, eps, is_train, lindisp, white_bkgd)
 
-    if want_rays and fused and N > 0:
+    if (want_rays or want_eps) and fused and N > 0:
         # CFNERF_F_RAY_GRAD: gradients reach ray_batch (columns 6, 7 - near / far - get zeros) whether or not the network is frozen.  The eval
         # branch is a graph in the reference too: it runs the stashed train-branch launch on the fixed eval latents (no jitter unless asked
         # for) and returns the eval structure, like NeRF_Flows.forward(is_test=True) with an input gradient wanted.
-        rgb_map, disp, depth, ent, raw, pts, wts = _RenderFn.apply(model.flat, model, ray_batch.to(torch.float32), t_vals, t_rand, eps,
+        # CFNERF_F_EPS_GRAD likewise: explicit latents that ask for a gradient get it from either branch, frozen network or not.
+        rgb_map, disp, depth, ent, raw, pts, wts = _RenderFn.apply(model.flat, model, ray_batch.to(torch.float32) if want_rays else rays, t_vals, t_rand, eps,
                                                                    flags | L.F_TRAIN, is_train, None, bool(retweights))
         ret = {'rgb_map': rgb_map, 'disp_map': disp, 'depth_map': depth}
         if is_train:
@@ -1162,8 +1187,9 @@ def _render_rays_hierarchical(ray_batch, network_fn, N_samples, N_importance, is
         z_all = torch.empty(N, S + N_importance, device=dev)
         L.check(L.lib().cfnerf_sample_pdf(L.ptr(rays), L.ptr(tv), L.ptr(tr), flags, L.ptr(c['weights']), L.ptr(u), N, S, K, N_importance,
                                           L.ptr(z_all), L.stream()), "cfnerf_sample_pdf")
-    if is_train and N > 0 and torch.is_grad_enabled() and model.flat.requires_grad:
-        rgb, disp, depth, ent, _raw, _pts, _wts = _RenderFn.apply(model.flat, model, rays, tv, None, eps, flags, False, z_all)
+    want_eps = torch.is_grad_enabled() and eps.requires_grad       # explicit latents that ask for a gradient: the fine pass gives it (CFNERF_F_EPS_GRAD)
+    if N > 0 and torch.is_grad_enabled() and ((is_train and model.flat.requires_grad) or want_eps):
+        rgb, disp, depth, ent, _raw, _pts, _wts = _RenderFn.apply(model.flat, model, rays, tv, None, eps, flags | L.F_TRAIN, False, z_all)
         ent = ent.reshape(1)
     else:
         f = _render_fwd(model, rays, tv, None, eps, flags, z_all)
@@ -1186,7 +1212,10 @@ def _render_rays_unfused(rays, model, network_fn, network_query_fn, t_vals, t_ra
     else:
         z_vals, pts0 = _sample_points(rays, t_vals, t_rand, lindisp)                                  # RUN:510-534
     # NeRF_Flows.forward consumes it (a custom query fn honours the launch's latents too); the network sees points: one row per point
-    model._next_eps = eps.repeat_interleave(S, 0) if eps.dim() == 3 else eps
+    if eps.dim() == 3 and _wants_grad(eps):     # (the same rows; an expand's adjoint is a plain sum - no atomics, unlike repeat_interleave's)
+        model._next_eps = eps[:, None].expand(eps.shape[0], S, *eps.shape[1:]).reshape(-1, *eps.shape[1:])
+    else:
+        model._next_eps = eps.repeat_interleave(S, 0) if eps.dim() == 3 else eps
     try:
         raw, loss_entropy = network_query_fn(pts0, viewdirs, network_fn, is_val=False, is_test=not is_train)
     finally:
@@ -1479,7 +1508,8 @@ def render_rays_warped(ray_batch, network_fn, sampler, is_train, lindisp=False, 
     z = w['z_vals']
     flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_TRAIN if is_train else 0)
     model._sync()
-    if N > 0 and (want_rays or (is_train and torch.is_grad_enabled() and model.flat.requires_grad)):
+    want_eps = _wants_grad(eps)                  # explicit latents that ask for a gradient (CFNERF_F_EPS_GRAD), either branch
+    if N > 0 and (want_rays or want_eps or (is_train and torch.is_grad_enabled() and model.flat.requires_grad)):
         # (rays that ask for a gradient on the eval branch: the stashed train-branch launch on the eval latents, as in render_rays)
         rgb_map, disp, depth, ent, raw, pts, wts = _RenderFn.apply(model.flat, model, ray_batch.to(torch.float32) if want_rays else rays, t_vals,
                                                                    None, eps, flags | L.F_TRAIN, is_train, z, bool(retweights))

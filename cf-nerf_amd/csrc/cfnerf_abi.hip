@@ -97,7 +97,7 @@ static int stash_bind(cfnerf_model* m, int64_t n, int s, int k) {
 // streams, the Q4 layout decision and a new generation (older backward passes are refused).
 static int forward_args(cfnerf_model* m, FwdArgs& a, int flags, int64_t n, int s, int K, bool points) {
     a.wp = m->d_packed; a.wp16 = m->d_packed16; a.flat = m->flat;
-    a.K = K; a.flags = (flags & 0xffff & ~(CFNERF_F_INPUT_GRAD | CFNERF_F_RAY_GRAD | CFNERF_F_COTANGENTS)) | flow_math_bits(m);      // (INPUT_GRAD / RAY_GRAD / COTANGENTS are the backward's business: Stash::flags)
+    a.K = K; a.flags = (flags & 0xffff & ~(CFNERF_F_INPUT_GRAD | CFNERF_F_RAY_GRAD | CFNERF_F_COTANGENTS | CFNERF_F_EPS_GRAD)) | flow_math_bits(m);      // (INPUT_GRAD / RAY_GRAD / COTANGENTS / EPS_GRAD are the backward's business: Stash::flags)
     if (!(flags & CFNERF_F_STASH)) return CFNERF_OK;
     if (int rc = stash_bind(m, n, s, K)) return rc;
     Stash& q = m->stash;
@@ -156,7 +156,8 @@ static int check_device(const cfnerf_model* m) {
 // a cfnerf_network_fwd stash for d loss / d x, CFNERF_F_RAY_GRAD the backward of a cfnerf_render_fwd stash for d loss / d rays and d loss / d z_vals,
 // CFNERF_F_COTANGENTS makes the backward of a cfnerf_render_fwd stash read its d_rgb_map argument as a host cfnerf_cotangents,
 // CFNERF_F_SEAM_GRAD belongs to the white_bkgd argument of cfnerf_composite_bwd alone, CFNERF_F_CULL turns the pts argument of
-// cfnerf_sample_points into a host cfnerf_cull (and travels in the white_bkgd argument of cfnerf_composite_fwd).
+// cfnerf_sample_points into a host cfnerf_cull (and travels in the white_bkgd argument of cfnerf_composite_fwd), CFNERF_F_EPS_GRAD asks the
+// backward of a cfnerf_render_fwd / cfnerf_network_fwd stash for d loss / d eps.
 // Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
@@ -173,6 +174,8 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_SEAM_GRAD (d_z_vals / d_rays_d of cfnerf_composite_bwd, passed in its white_bkgd argument)", who);
     if (flags & CFNERF_F_CULL & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_CULL (the occupancy-grid descriptor of cfnerf_sample_points; cfnerf_composite_fwd takes the bit in its white_bkgd argument)", who);
+    if (flags & CFNERF_F_EPS_GRAD & ~allowed)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_EPS_GRAD (the latent gradient of cfnerf_render_fwd / cfnerf_network_fwd with CFNERF_F_STASH, written by their backward)", who);
     return CFNERF_OK;
 }
 
@@ -193,7 +196,7 @@ static int check_geometry_flags(int flags) {
     static const struct { int bit; const char* name; } bad[] = {{CFNERF_F_TRAIN, "CFNERF_F_TRAIN"}, {CFNERF_F_STASH, "CFNERF_F_STASH"},
                                                                 {CFNERF_F_EPS_ROWS, "CFNERF_F_EPS_ROWS"}, {CFNERF_F_KSTATS_EXT, "CFNERF_F_KSTATS_EXT"},
                                                                 {CFNERF_F_INPUT_GRAD, "CFNERF_F_INPUT_GRAD"}, {CFNERF_F_RAY_GRAD, "CFNERF_F_RAY_GRAD"},
-                                                                {CFNERF_F_COTANGENTS, "CFNERF_F_COTANGENTS"}};
+                                                                {CFNERF_F_COTANGENTS, "CFNERF_F_COTANGENTS"}, {CFNERF_F_EPS_GRAD, "CFNERF_F_EPS_GRAD"}};
     for (const auto& b : bad)
         if (flags & b.bit)
             return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY is an eval-branch launch without the colour branch: it cannot be combined with %s", b.name);
@@ -345,7 +348,15 @@ int cfnerf_render_fwd(cfnerf_model* m, const float* rays, const float* t_vals, c
                       float* raw_opt, float* weights_opt, float* pts_opt, float* kstats_opt, float* entropy_out, cfnerf_stream s) {
     if (int rc = check_common(m, K)) return rc;
     if (N < 0 || S < 1) return fail(CFNERF_E_INVALID, "bad N/S");
-    if (int rc = refuse_mode_flags(flags, CFNERF_F_KSTATS_EXT | CFNERF_F_GEOMETRY | CFNERF_F_RAY_GRAD | CFNERF_F_COTANGENTS, "cfnerf_render_fwd")) return rc;
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_KSTATS_EXT | CFNERF_F_GEOMETRY | CFNERF_F_RAY_GRAD | CFNERF_F_COTANGENTS | CFNERF_F_EPS_GRAD, "cfnerf_render_fwd")) return rc;
+    if (flags & CFNERF_F_EPS_GRAD) {
+        if (flags & CFNERF_F_GEOMETRY)
+            return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_GRAD cannot be combined with CFNERF_F_GEOMETRY (a geometry-only launch keeps no stash to differentiate)");
+        if (!(flags & CFNERF_F_STASH))
+            return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_GRAD needs CFNERF_F_STASH (d loss / d eps is written by cfnerf_render_bwd from the stashed forward)");
+        if (flags & CFNERF_F_KSTATS_EXT)
+            return fail(CFNERF_E_UNSUPPORTED, "CFNERF_F_EPS_GRAD cannot be combined with CFNERF_F_KSTATS_EXT (evaluation metrics: render without a stash)");
+    }
     if (flags & CFNERF_F_COTANGENTS) {
         if (flags & CFNERF_F_GEOMETRY)
             return fail(CFNERF_E_INVALID, "CFNERF_F_COTANGENTS cannot be combined with CFNERF_F_GEOMETRY (a geometry-only launch keeps no stash to differentiate)");
@@ -445,7 +456,9 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
     if (int rc = check_common(m, K)) return rc;
     const bool geom = flags & CFNERF_F_GEOMETRY;
     if (geom) if (int rc = check_geometry_flags(flags)) return rc;
-    if (int rc = refuse_mode_flags(flags, CFNERF_F_GEOMETRY | CFNERF_F_INPUT_GRAD, "cfnerf_network_fwd")) return rc;
+    if (int rc = refuse_mode_flags(flags, CFNERF_F_GEOMETRY | CFNERF_F_INPUT_GRAD | CFNERF_F_EPS_GRAD, "cfnerf_network_fwd")) return rc;
+    if ((flags & CFNERF_F_EPS_GRAD) && !(flags & CFNERF_F_STASH))
+        return fail(CFNERF_E_INVALID, "CFNERF_F_EPS_GRAD needs CFNERF_F_STASH (d loss / d eps is written by cfnerf_network_bwd from the stashed forward)");
     if ((flags & CFNERF_F_INPUT_GRAD) && !(flags & CFNERF_F_STASH))
         return fail(CFNERF_E_INVALID, "CFNERF_F_INPUT_GRAD needs CFNERF_F_STASH (d loss / d x is written by cfnerf_network_bwd from the stashed forward)");
     if (P < 0 || P > 0x7fffffff) return fail(CFNERF_E_INVALID, "bad P");

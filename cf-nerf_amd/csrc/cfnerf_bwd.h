@@ -39,11 +39,19 @@ struct BwdArgs {
     int32_t db_h, db_feat, db_v, db_ha, db_hr, db_theta;  // column offsets inside a dbp row
 };
 
+// ... and what tail_eps_kernel, launched BESIDE one of the two (CFNERF_F_EPS_GRAD), writes: d_eps_rows [N,K,4] in the caller's grad_flat.  Null: no such launch.
+struct TailEps {
+    float* rows = nullptr;
+};
+
 // the flow-adjoint kernels live in cfnerf_tail.hip (a translation unit compiled without the SLP vectoriser)
-hipError_t launch_tail_bwd(const TailArgs& ta, const TailCot& cot, int64_t n_rays, int ksplit, hipStream_t st);
-// eps_rows: eps is [P,K,4], one row per point (CFNERF_F_EPS_ROWS); else [K,4]
+hipError_t launch_tail_bwd(const TailArgs& ta, const TailCot& cot, const TailEps& eg, int64_t n_rays, int ksplit, hipStream_t st);
+// eps_rows: eps is [P,K,4], one row per point (CFNERF_F_EPS_ROWS); else [K,4].  eps_out: d_eps_rows [P,K,4] (CFNERF_F_EPS_GRAD: flows_eps_kernel) or null
 hipError_t launch_flows_bwd(const float* raw, const float* theta, const float* eps, int eps_rows, const float* flat, const float* d_raw,
-                            const float* d_ent, int64_t P, int K, float* g_theta, float* gms_partials, unsigned* grid_out, hipStream_t st);
+                            const float* d_ent, int64_t P, int K, float* g_theta, float* gms_partials, float* eps_out, unsigned* grid_out,
+                            hipStream_t st);
+// d_eps [K,4] = sum of the rows [n,K,4] in a fixed order (CFNERF_F_EPS_GRAD, both paths)
+hipError_t launch_reduce_eps(const float* rows, int64_t n, int K, float* d_eps, hipStream_t st);
 
 // d loss / d x of a points-mode stash (CFNERF_F_INPUT_GRAD; cfnerf_inputgrad.hip): reads the final g_h / g_v and the flat weights
 struct InputGradArgs {

@@ -1233,6 +1233,16 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
     int64_t gms_rows = 0;
     if (m->timing == 1) HIPCHK(hipEventRecord(m->ev0[1], st));
     const float* const eps = q.eps_rows ? q.eps_rows : m->d_eps;      // (rows: the caller's buffer; q.flags carries CFNERF_F_EPS_ROWS)
+    // CFNERF_F_EPS_GRAD: d_eps [K,4] and d_eps_rows [n,K,4] behind the blocks the stash already asks for (cfnerf.h); per-launch quantities,
+    // written by the first stage's eps variant and one reduction - the caller's grad_flat is the only new memory
+    float *d_eps_out = nullptr, *d_eps_rows = nullptr;
+    if (q.flags & CFNERF_F_EPS_GRAD) {
+        int64_t base_end = n_params;
+        if (!points && (q.flags & CFNERF_F_RAY_GRAD)) base_end = (n_params + 63) / 64 * 64 + (N * 11 + 63) / 64 * 64 + N * (int64_t)q.S;
+        if (points && (q.flags & CFNERF_F_INPUT_GRAD)) base_end = (n_params + 63) / 64 * 64 + P * (int64_t)(m->plan.tab.ic + m->plan.tab.icv);
+        const int64_t e_off = (base_end + 63) / 64 * 64, er_off = e_off + (4 * (int64_t)q.K + 63) / 64 * 64;
+        d_eps_out = grad_flat + e_off; d_eps_rows = grad_flat + er_off;
+    }
     if (!points) {
         TailArgs ta{};
         ta.raw = q.raw; ta.theta = q.theta; ta.at = q.at; ta.z = q.z; ta.rays = q.rays; ta.eps = eps; ta.flat = m->flat;
@@ -1243,14 +1253,17 @@ static int backward_stashed(cfnerf_model* m, bool points, uint64_t stash_generat
         ksplit = tail_parts(N, q.K, std::min(m->n_cu, kMaxCu));      // 1, 2 or 4: the parts of a ray are waves of ONE 4-wave workgroup and
         ta.ksplit = ksplit;                                          // meet in LDS, so ONE g_theta row per point leaves the kernel
         gms_rows = N * ksplit;
-        HIPCHK(launch_tail_bwd(ta, tc, N, ksplit, st));
+        TailEps te;
+        te.rows = d_eps_rows;                                        // (CFNERF_F_EPS_GRAD: tail_eps_kernel, with or without cotangents)
+        HIPCHK(launch_tail_bwd(ta, tc, te, N, ksplit, st));
     } else {
         unsigned grid = 0;
-        HIPCHK(launch_flows_bwd(q.raw, q.theta, eps, q.eps_rows ? 1 : 0, m->flat, d_out, d_entropy, P, q.K, q.g_theta, q.gms, &grid, st));
+        HIPCHK(launch_flows_bwd(q.raw, q.theta, eps, q.eps_rows ? 1 : 0, m->flat, d_out, d_entropy, P, q.K, q.g_theta, q.gms, d_eps_rows, &grid, st));
         gms_rows = (int64_t)grid * kWaves;                       // one row per wave (waves past P contribute zeros)
     }
     hipLaunchKernelGGL(reduce_gms_kernel, dim3(1), dim3(256), 0, st, q.gms, gms_rows, m->flat, d_entropy, grad_flat, accumulate);
     HIPCHK(hipGetLastError());
+    if (d_eps_rows) HIPCHK(launch_reduce_eps(d_eps_rows, points ? P : N, q.K, d_eps_out, st));
     if (m->timing == 1) HIPCHK(hipEventRecord(m->ev1[1], st));
 
     // ---- 1b. CFNERF_F_RAY_GRAD: the composite's adjoint in z and |d| needs only the stash and the cotangents.  Outside the event pairs of the

@@ -2,6 +2,7 @@
 //   tail_bwd_kernel   (fused path)   adjoint of raw2outputs (RUN:424-452) + of the K conditional flows (FLW:225-268, MOD:263-286)
 //   tail_cot_kernel   (fused path, CFNERF_F_COTANGENTS with a cotangent for disp_map, weights or raw) the same body (cfnerf_tail_body.h) + those three
 //   flows_bwd_kernel  (unfused seam) adjoint of the K flows + entropy terms of NeRF_Flows.forward (MOD:225-291) given d loss / d raw
+//   tail_eps_kernel, flows_eps_kernel, reduce_eps_kernel (CFNERF_F_EPS_GRAD) the two bodies + d loss / d eps per ray / point, and its sum
 // Both are long straight-line scalar code (the unrolled adjoint of four 3 x 3 triangular flow steps per (sample, latent)) on one wave per
 // SIMD.  This file is compiled with -fno-slp-vectorize (cf-nerf_amd/build.py): left on, the SLP vectoriser pairs the arithmetic into
 // v_pk_mul / v_pk_add / v_pk_fma and then needs ~200 v_mov per (chunk, latent) to line the operands up in register pairs; that pushes the
@@ -151,7 +152,9 @@ __device__ __forceinline__ void store_gtheta_row(float* __restrict__ row, const 
 __global__ __launch_bounds__(kThreads, 2)
 void tail_bwd_kernel(const TailArgs A) {
 #define CFN_TAIL_COT 0
+#define CFN_TAIL_EPS 0
 #include "cfnerf_tail_body.h"
+#undef CFN_TAIL_EPS
 #undef CFN_TAIL_COT
 }
 
@@ -159,7 +162,20 @@ void tail_bwd_kernel(const TailArgs A) {
 __global__ __launch_bounds__(kThreads, 2)
 void tail_cot_kernel(const TailArgs A, const TailCot C) {
 #define CFN_TAIL_COT 1
+#define CFN_TAIL_EPS 0
 #include "cfnerf_tail_body.h"
+#undef CFN_TAIL_EPS
+#undef CFN_TAIL_COT
+}
+
+// CFNERF_F_EPS_GRAD: the cotangent body for this ray's rows of d loss / d eps alone, launched beside one of the two kernels above (an opt-in
+// launch, not the train step's); the merge rows are dead here, so its LDS is carry + cot + the 8 KB of `epsg`; no scratch (tools/kernel_regs.py)
+__global__ __launch_bounds__(kThreads, 2)
+void tail_eps_kernel(const TailArgs A, const TailCot C, const TailEps E) {
+#define CFN_TAIL_COT 1
+#define CFN_TAIL_EPS 1
+#include "cfnerf_tail_body.h"
+#undef CFN_TAIL_EPS
 #undef CFN_TAIL_COT
 }
 
@@ -173,64 +189,68 @@ __global__ __launch_bounds__(kThreads)
 void flows_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ theta, const float* __restrict__ eps, int eps_rows,
                       const float* __restrict__ flat, const float* __restrict__ d_raw, const float* __restrict__ d_ent, int64_t P, int K,
                       float* __restrict__ g_theta, float* __restrict__ gms_partials) {
-#pragma clang fp contract(fast)
-    const int lane = lane_id_opaque(), wave = wave_id();
-    const int64_t pi = (int64_t)blockIdx.x * kThreads + wave * 64 + lane;
-    const bool valid = pi < P;
-    const int64_t p = valid ? pi : 0;
-    const float cE = -((d_ent != nullptr) ? d_ent[0] : 0.f) / (float)((double)P * (double)K);
-    const float a_mean = flat[0], a_std = flat[1];
-    const float r_mean[3] = {flat[2], flat[3], flat[4]};
-    const float r_std[3] = {flat[5], flat[6], flat[7]};
-    float th[84], gms[8];
-    GReg gth;
-    const float* const e_pt = eps_rows ? eps + p * K * 4 : eps;            // CFNERF_F_EPS_ROWS: this point's [K,4] row
-    {
-        const f32x4* tp = reinterpret_cast<const f32x4*>(theta + p * kThetaAll);
-#pragma unroll
-        for (int q = 0; q < 18; ++q) { const f32x4 v = tp[q]; th[q * 4] = v[0]; th[q * 4 + 1] = v[1]; th[q * 4 + 2] = v[2]; th[q * 4 + 3] = v[3]; }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { const f32x4 v = tp[kThetaRgb / 4 + q]; th[72 + q * 4] = v[0]; th[73 + q * 4] = v[1]; th[74 + q * 4] = v[2]; th[75 + q * 4] = v[3]; }
+#define CFN_FLOWS_EPS 0
+#include "cfnerf_flows_bwd_body.h"
+#undef CFN_FLOWS_EPS
+}
+
+// CFNERF_F_EPS_GRAD of a points stash, launched beside flows_bwd_kernel: the same body for the point's [K,4] row of d loss / d eps alone, into
+// eps_out [P,K,4] (16-byte stores, one per latent); g_theta / gms_partials are not written
+__global__ __launch_bounds__(kThreads)
+void flows_eps_kernel(const float* __restrict__ raw, const float* __restrict__ theta, const float* __restrict__ eps, int eps_rows,
+                      const float* __restrict__ flat, const float* __restrict__ d_raw, const float* __restrict__ d_ent, int64_t P, int K,
+                      float* __restrict__ g_theta, float* __restrict__ gms_partials, float* __restrict__ eps_out) {
+#define CFN_FLOWS_EPS 1
+#include "cfnerf_flows_bwd_body.h"
+#undef CFN_FLOWS_EPS
+}
+
+// d_eps [K,4] = the sum of d_eps_rows [n,K,4] over its n rows (rays of a fused launch, points of a seam launch) in a fixed order: one
+// workgroup per latent, double accumulators, rounded once - like reduce_gms_kernel.  The rows already hold the base log-normal's direct
+// term (each its own share of it), so it enters the sum exactly once.
+__global__ __launch_bounds__(256)
+void reduce_eps_kernel(const float* __restrict__ rows, int64_t n, int K, float* __restrict__ d_eps) {
+    __shared__ double sh[4][256];
+    const int k = blockIdx.x;
+    double s[4] = {0, 0, 0, 0};
+    for (int64_t r = threadIdx.x; r < n; r += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(rows + (r * K + k) * 4);
+        s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
     }
-    gth.clear();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gms[i] = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const f32x4 rv = *reinterpret_cast<const f32x4*>(raw + (((p >> 6) * K + k) * 64 + (p & 63)) * 4);    // tile-transposed stash: [tile p / 64][k][row p % 64][4]
-        f32x4 g; g[0] = g[1] = g[2] = g[3] = 0.f;
-        if (d_raw != nullptr) g = *reinterpret_cast<const f32x4*>(d_raw + (p * K + k) * 4);
-        const f32x4 e = *reinterpret_cast<const f32x4*>(e_pt + k * 4);
-        const float c0 = t_sigmoid(rv[0]), c1 = t_sigmoid(rv[1]), c2 = t_sigmoid(rv[2]), sg = t_sigmoid(rv[3]);
-        float ga = g[3] + cE * (1.f - sg);                                     // + d(-mean(a - softplus a))  MOD:263
-        float gz[3] = {g[0] + cE * (1.f - 2.f * c0), g[1] + cE * (1.f - 2.f * c1), g[2] + cE * (1.f - 2.f * c2)};   // MOD:278
-        if (!valid) { ga = 0.f; gz[0] = gz[1] = gz[2] = 0.f; }
-        flows_adjoint(th, gth, gms, e, a_mean, a_std, r_mean, r_std, ga, gz, cE, valid);
+    for (int i = 0; i < 4; ++i) sh[i][threadIdx.x] = s[i];
+    __syncthreads();
+    for (int d = 128; d >= 1; d >>= 1) {
+        if ((int)threadIdx.x < d) for (int i = 0; i < 4; ++i) sh[i][threadIdx.x] += sh[i][threadIdx.x + d];
+        __syncthreads();
     }
-    if (valid) store_gtheta_row(g_theta + p * kThetaAll, th, gth);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gms[i] = wave_sum(gms[i]);
-    if (lane == 0) {
-        const int64_t row = (int64_t)blockIdx.x * kWaves + wave;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) gms_partials[row * 8 + i] = gms[i];
-    }
+    if (threadIdx.x < 4) d_eps[k * 4 + threadIdx.x] = (float)sh[threadIdx.x][0];
 }
 
 
 // ---- host launchers (cfnerf_bwd.h)
-hipError_t launch_tail_bwd(const TailArgs& ta, const TailCot& cot, int64_t n_rays, int ksplit, hipStream_t st) {
+hipError_t launch_tail_bwd(const TailArgs& ta, const TailCot& cot, const TailEps& eg, int64_t n_rays, int ksplit, hipStream_t st) {
     const dim3 grid((unsigned)((n_rays * ksplit + kWaves - 1) / kWaves));
+    if (eg.rows != nullptr) hipLaunchKernelGGL(tail_eps_kernel, grid, dim3(kThreads), 0, st, ta, cot, eg);      // (CFNERF_F_EPS_GRAD: beside the launch below, cotangents or not)
     if (cot.any()) hipLaunchKernelGGL(tail_cot_kernel, grid, dim3(kThreads), 0, st, ta, cot);
     else hipLaunchKernelGGL(tail_bwd_kernel, grid, dim3(kThreads), 0, st, ta);
     return hipGetLastError();
 }
 
 hipError_t launch_flows_bwd(const float* raw, const float* theta, const float* eps, int eps_rows, const float* flat, const float* d_raw,
-                            const float* d_ent, int64_t P, int K, float* g_theta, float* gms_partials, unsigned* grid_out, hipStream_t st) {
+                            const float* d_ent, int64_t P, int K, float* g_theta, float* gms_partials, float* eps_out, unsigned* grid_out,
+                            hipStream_t st) {
     const unsigned grid = (unsigned)((P + kThreads - 1) / kThreads);
     if (grid_out) *grid_out = grid;
+    if (eps_out != nullptr)                                  // CFNERF_F_EPS_GRAD: beside the launch below
+        hipLaunchKernelGGL(flows_eps_kernel, dim3(grid), dim3(kThreads), 0, st, raw, theta, eps, eps_rows, flat, d_raw, d_ent, P, K, g_theta,
+                           gms_partials, eps_out);
     hipLaunchKernelGGL(flows_bwd_kernel, dim3(grid), dim3(kThreads), 0, st, raw, theta, eps, eps_rows, flat, d_raw, d_ent, P, K, g_theta,
                        gms_partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_reduce_eps(const float* rows, int64_t n, int K, float* d_eps, hipStream_t st) {
+    hipLaunchKernelGGL(reduce_eps_kernel, dim3((unsigned)K), dim3(256), 0, st, rows, n, K, d_eps);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
-// cfnerf_tail_body.h - the body of tail_bwd_kernel and tail_cot_kernel (cfnerf_tail.hip), included ONCE PER KERNEL between the braces of
-// the kernel, with CFN_TAIL_COT 0 / 1: `A` is the kernel's TailArgs and, with CFN_TAIL_COT, `C` its TailCot.
+// cfnerf_tail_body.h - the body of tail_bwd_kernel, tail_cot_kernel and tail_eps_kernel (cfnerf_tail.hip), included ONCE PER KERNEL between
+// the braces of the kernel, with CFN_TAIL_COT 0 / 1 and CFN_TAIL_EPS 0 / 1: `A` is the kernel's TailArgs, with CFN_TAIL_COT `C` its TailCot and
+// with CFN_TAIL_EPS `E` its TailEps.
 // Shared as TEXT, not as a __forceinline__ template on a bool: tail_bwd_kernel lives at the register limit, and its code generation follows the
 // token stream - handed to a function template (by reference, by value or field by field) the kernel allocated its scalar registers and
 // scheduled its scalar code differently from the build before (5 instead of 7 SGPRs in VGPR lanes at best, profiles/r12_kernel_regs.txt).
@@ -11,6 +12,16 @@
 //   branch included); the walk then adds Gd' to Gd and Ga to g, as the white-background term enters g.  d_weights is added to g, d_raw to
 //   (gz, ga) where they are formed.  The three operands are loaded at their point of use through bounded buffer descriptors, not in the
 //   one-latent-ahead prefetch: the kernel lives at the register limit.
+// CFN_TAIL_EPS 1 (CFNERF_F_EPS_GRAD, on top of CFN_TAIL_COT 1 - a null TailCot costs a few scalar branches, and one variant serves stashes with and
+// without cotangents): d loss / d eps of this ray's [K,4] latent row, and NOTHING else - the kernel runs BESIDE tail_bwd_kernel / tail_cot_kernel,
+// which write g_theta and the base-Gaussian partials as ever.  (One kernel for both was tried first: the compiler contracts the shared adjoint's
+// multiply-adds differently in a different kernel - v_fma in one, v_mul + v_add in the other for the same source line - and the parameter gradient
+// of a stash with the flag moved by one unit in the last place at a few entries.  "Nothing else moves" is a contract, so the launches that write
+// what already existed stay the ones of before, and this variant drops their stores: the 84 g_theta accumulators, the k-part merge and its
+// barriers are dead code here.)  flows_adjoint ends in d loss / d z0 per (sample, latent) and folds it over k into the base-Gaussian sums; handed
+// a zeroed 8-vector in place of `gms`, it leaves this lane's d z0 there (entries 0 and 2..4).  Four wave_sums per (chunk, latent) add the lanes,
+// an LDS row per latent adds the chunks (written by lane 0, as `carry` is), and at the end the wave writes rows k in [k_lo, k_hi) of its ray:
+// a wave owns its (ray, k-part), so the parts never meet.  With CFN_TAIL_EPS 0 the preprocessor leaves the two kernels of before.
 #pragma clang fp contract(fast)
     __shared__ float carry[kWaves][kMaxK][3];              // per latent: (g, x, D) of the first sample of the chunk behind (comp_adjoint_D)
     // merge (ksplit 2 or 4, so a ray's parts are waves of ONE workgroup): the parts past the first publish their 84 partial sums per
@@ -28,7 +39,11 @@
     static_assert(kWaves % kTailParts == 0 && (kTailParts & (kTailParts - 1)) == 0, "a ray's k-parts must be waves of one workgroup");
     const bool merge = A.ksplit > 1;                       // (tail_parts: 1, 2 or 4 - the divisors of the workgroup's 4 waves)
     const bool live = ray_u < A.N;
+#if CFN_TAIL_EPS
+    if (!live) return;                                     // (no merge, hence no barrier in this variant: a wave past the last ray just leaves)
+#else
     if (!live && !merge) return;                           // (merge: every wave of the workgroup keeps step with the barriers below)
+#endif
     const int64_t ray = live ? ray_u : 0;                  // (a wave past the last ray addresses ray 0 and touches nothing)
     const int S = A.S, K = A.K;
     const int Kp = (K + A.ksplit - 1) / A.ksplit, k_lo = part * Kp, k_hi = min(K, k_lo + Kp);
@@ -47,6 +62,10 @@
     for (int i = 0; i < 8; ++i) gms[i] = 0.f;
 
     const int nch = (S + 63) / 64;
+#if CFN_TAIL_EPS
+    __shared__ float epsg[kWaves][kMaxK][4];               // per latent: sum over the ray's samples of d loss / d z0 (rgb, alpha)
+    for (int k = lane; k < K; k += 64) { epsg[wave][k][0] = 0.f; epsg[wave][k][1] = 0.f; epsg[wave][k][2] = 0.f; epsg[wave][k][3] = 0.f; }
+#endif
 #if CFN_TAIL_COT
     // pre-pass: depth_k = sum_s w_s z_s and acc_k = sum_s w_s of this wave's latents from the stashed (e, T) stream, then (Gd', Ga) per latent
     __shared__ float cot[kWaves][kMaxK][2];
@@ -82,7 +101,9 @@
     }
 #endif
     for (int ch = nch - 1; ch >= 0; --ch) {
+#if !CFN_TAIL_EPS
         if (!live) { __syncthreads(); __syncthreads(); continue; }      // (merge only: a wave past the last ray)
+#endif
         const int s = ch * 64 + lane;
         const bool valid = s < S;
         const int64_t p = ray * (int64_t)S + (valid ? s : 0);
@@ -172,8 +193,19 @@
 #endif
             if (!valid) { ga = 0.f; gz[0] = gz[1] = gz[2] = 0.f; }
 
+#if CFN_TAIL_EPS
+            float gl[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) gl[i] = 0.f;
+            flows_adjoint(th, gth, gl, cur.e, a_mean, a_std, r_mean, r_std, ga, gz, cE, valid);
+            // (gl[0] = d z0 of the density latent, gl[2..4] of the colour latents)
+            const float e0 = wave_sum(gl[2]), e1 = wave_sum(gl[3]), e2 = wave_sum(gl[4]), e3 = wave_sum(gl[0]);     // (lanes past S hold zeros)
+            if (lane == 0) { epsg[wave][k][0] += e0; epsg[wave][k][1] += e1; epsg[wave][k][2] += e2; epsg[wave][k][3] += e3; }
+#else
             flows_adjoint(th, gth, gms, cur.e, a_mean, a_std, r_mean, r_std, ga, gz, cE, valid);
+#endif
         }
+#if !CFN_TAIL_EPS
         if (merge) {
             if (part != 0) {
 #pragma unroll
@@ -191,11 +223,30 @@
         } else if (valid) {
             store_gtheta_row(A.g_theta + p * kThetaAll, th, gth);
         }
+#endif
     }
     if (!live) return;
+#if CFN_TAIL_EPS
+    // this ray's rows k in [k_lo, k_hi) of d_eps_rows [N,K,4] (an empty last part writes nothing): the chain through z0 = eps std + mean, plus
+    // the ray's share of the base log-normal's direct term (MOD:268,283,286: -d_entropy eps / (K N), a colour latent a third of it)
+    wave_lds_turn();
+    {
+        const float cB = -((A.d_ent != nullptr) ? A.d_ent[0] : 0.f) / (float)((double)A.N * (double)K);
+        for (int k = k_lo + lane; k < k_hi; k += 64) {
+            const f32x4 ev = *reinterpret_cast<const f32x4*>(eps_ray + k * 4);
+            f32x4 o;
+            o[0] = epsg[wave][k][0] * r_std[0] + cB * (1.f / 3.f) * ev[0];
+            o[1] = epsg[wave][k][1] * r_std[1] + cB * (1.f / 3.f) * ev[1];
+            o[2] = epsg[wave][k][2] * r_std[2] + cB * (1.f / 3.f) * ev[2];
+            o[3] = epsg[wave][k][3] * a_std + cB * ev[3];
+            *reinterpret_cast<f32x4*>(E.rows + (ray * K + k) * 4) = o;
+        }
+    }
+#else
 #pragma unroll
     for (int i = 0; i < 8; ++i) gms[i] = wave_sum(gms[i]);
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) A.gms_partials[unit * 8 + i] = gms[i];
     }
+#endif

@@ -29,7 +29,9 @@ def pack(eps_alpha, eps_rgb):
 
 def to_device(eps, device):
     """Latents on ``device``; host tensors through pinned memory, not blocking the host (a pageable copy would stall the launch queue)."""
-    return eps.to(device) if eps.is_cuda else eps.pin_memory().to(device, non_blocking=True)
+    if eps.is_cuda or (torch.is_grad_enabled() and eps.requires_grad):      # (latents on the autograd graph: one differentiable copy)
+        return eps.to(device)
+    return eps.pin_memory().to(device, non_blocking=True)
 
 
 def check_rows(eps, n, what, hint=" (per-netchunk latents go through netchunk_eps_rows)"):
@@ -65,9 +67,9 @@ def netchunk_count(N, S, netchunk, chunk=None):
     return sum(network_calls(n * S, netchunk) for _, n in ray_cuts(N, chunk))
 
 
-def netchunk_eps_rows(eps_chunks, N, S, netchunk, chunk=None):
-    """Expand per-netchunk latents ``eps_chunks [C,K,4]`` (in draw order) to ray rows ``[N,K,4]``: ray i gets the latents of the network
-    call that evaluates its points.  Needs ``netchunk % S == 0`` (see the refusal below)."""
+def netchunk_row_index(N, S, netchunk, chunk=None, with_count=False):
+    """The latent pair (in draw order) of every ray of an N-ray batch, a non-decreasing host index ``[N]``: ray i gets the latents of the
+    network call that evaluates its points.  Needs ``netchunk % S == 0`` (see the refusal below)."""
     netchunk, S = int(netchunk), int(S)
     if netchunk % S:
         raise NotImplementedError(f"netchunk ({netchunk}) is not a multiple of the samples per ray ({S}): the reference then changes "
@@ -77,10 +79,45 @@ def netchunk_eps_rows(eps_chunks, N, S, netchunk, chunk=None):
     for _, n in ray_cuts(N, chunk):
         idx.append(base + torch.arange(n) // per)
         base += network_calls(n * S, netchunk)
+    idx = torch.cat(idx) if idx else torch.zeros(0, dtype=torch.long)
+    return (idx, base) if with_count else idx
+
+
+def netchunk_eps_rows(eps_chunks, N, S, netchunk, chunk=None):
+    """Expand per-netchunk latents ``eps_chunks [C,K,4]`` (in draw order) to ray rows ``[N,K,4]`` (``netchunk_row_index``)."""
+    idx, base = netchunk_row_index(N, S, netchunk, chunk, with_count=True)
     if eps_chunks.shape[0] != base:
         raise ValueError(f"{eps_chunks.shape[0]} latent pairs given; N={N}, S={S}, netchunk={netchunk}, chunk={chunk} needs {base}")
-    idx = torch.cat(idx) if idx else torch.zeros(0, dtype=torch.long)
+    if torch.is_grad_enabled() and eps_chunks.requires_grad:
+        return _PairsToRows.apply(eps_chunks, idx)
     return eps_chunks.index_select(0, idx.to(eps_chunks.device)).contiguous()
+
+
+class _PairsToRows(torch.autograd.Function):
+    """``netchunk_eps_rows`` for pairs that ask for a gradient: the same ``index_select``, with a deterministic adjoint.  The rows of a pair
+    are one contiguous segment (``idx`` is non-decreasing), so d pairs[c] is a plain sum over the segment - torch's own backward of
+    ``index_select`` adds with atomics on the GPU, and the latent gradient is bit-reproducible from the kernels up."""
+
+    @staticmethod
+    def forward(ctx, pairs, idx):
+        ctx.counts = torch.bincount(idx, minlength=pairs.shape[0]).tolist()      # (idx is a host tensor: no device round trip)
+        return pairs.index_select(0, idx.to(pairs.device)).contiguous()
+
+    @staticmethod
+    def backward(ctx, d_rows):
+        return rows_to_pairs_sum(d_rows, ctx.counts), None
+
+
+def rows_to_pairs_sum(rows, counts):
+    """Sum rows ``[N,...]`` over consecutive segments of ``counts[c]`` rows each -> ``[C,...]``: the adjoint of pairs -> rows, in a fixed
+    order and without atomics (``_PairsToRows.backward``, ``train.Trainer`` for the pairs' latent gradient).  ``counts``: a host list, e.g.
+    ``torch.bincount(netchunk_row_index(...), minlength=C).tolist()``."""
+    out, r0 = rows.new_zeros(len(counts), *rows.shape[1:]), 0
+    for c, n in enumerate(counts):
+        if n:
+            out[c] = rows[r0:r0 + n].sum(0)
+        r0 += n
+    return out
 
 
 def netchunk_eps_point_rows(eps_chunks, P, netchunk):

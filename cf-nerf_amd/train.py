@@ -107,18 +107,29 @@ class Trainer:
     ``ray_grad=True`` (one rank): ``forward_backward`` / ``step`` also leave ``self.d_rays [N,11]`` = d loss / d (the packed rays) and
     ``self.d_z [N,S]`` = d loss / d z_vals of the step's WHOLE loss (means over the full batch), rows in launch order - colour rays, then
     depth rays (CFNERF_F_RAY_GRAD; columns 6, 7 of ``d_rays`` - near / far - are zero, cfnerf.h).  ``api.pack_rays(...).backward(trainer.d_rays)``
-    chains them into a pose.  The default changes nothing: same buffers, same launches."""
+    chains them into a pose.  The default changes nothing: same buffers, same launches.
+
+    ``latent_grad=True`` (one rank): ``forward_backward`` / ``step`` also leave ``self.d_eps`` = d loss / d (the step's latents) of the step's
+    WHOLE loss, summed over the slices of a sliced step (CFNERF_F_EPS_GRAD): ``[K,4]`` for one latent set, ``[C,K,4]`` - one per pair, in
+    draw order - in netchunk mode, ``[N,K,4]`` for explicit per-ray rows; columns rgb then alpha, like the latents.  The default changes
+    nothing: same buffers, same launches.  ``forward_backward_hierarchical`` / ``step_hierarchical`` refuse the option (their passes never
+    carry the flag: the blocks behind the parameter gradient are sized by ``forward_backward`` alone)."""
 
     def __init__(self, net, lrate=5e-4, lrate_decay=250, beta1=0.0, world_size=1, group=None, start=0, force_allreduce=False,
                  overlap_comm=False, time_comm=False, max_rays_per_launch=None, latent_draws="launch", netchunk=1024 * 64, chunk=1024 * 32,
-                 depth_lambda=0.0, ray_grad=False):
+                 depth_lambda=0.0, ray_grad=False, latent_grad=False):
         if latent_draws not in LT.LATENT_DRAWS:
             raise ValueError(f"latent_draws must be one of {LT.LATENT_DRAWS}, got {latent_draws!r}")
         if ray_grad and (int(world_size) > 1 or force_allreduce):
             raise NotImplementedError("Trainer(ray_grad=True) with world_size > 1 / force_allreduce: the ray blocks of CFNERF_F_RAY_GRAD lie behind "
                                       "the parameter gradient in the buffer whose tail the gradient exchange uses for the next step's latents")
+        if latent_grad and (int(world_size) > 1 or force_allreduce):
+            raise NotImplementedError("Trainer(latent_grad=True) with world_size > 1 / force_allreduce: the latent blocks of CFNERF_F_EPS_GRAD lie behind "
+                                      "the parameter gradient in the buffer whose tail the gradient exchange uses for the next step's latents")
         self.ray_grad = bool(ray_grad)
         self.d_rays = self.d_z = None
+        self.latent_grad = bool(latent_grad)
+        self.d_eps = None
         self.latent_draws, self.netchunk, self.chunk = latent_draws, int(netchunk), (int(chunk) if chunk else None)
         # max_rays_per_launch: a step's shard larger than this is walked in EQUAL slices (forward -> loss -> backward per slice, the
         # gradient accumulated by cfnerf_render_bwd_accumulate, ONE exchange and ONE Adam step at the end): the train-step workspace
@@ -313,8 +324,28 @@ class Trainer:
             self.grad = self.gbuf[:self.net.n_params]
             self._xplan = None
 
+    def _latent_grad_buffers(self, eps, S, n_max):
+        """The step's latent gradient, zeroed (``[K,4]`` or one row per ray), and the gradient buffer grown to hold the latent blocks of its
+        largest pass (``n_max`` rays) behind the parameter gradient and the ray blocks (cfnerf.h, CFNERF_F_EPS_GRAD)"""
+        dev, n = self.net.flat.device, self.net.n_params
+        self._d_eps_acc = torch.zeros(eps.shape, device=dev)
+        need = L.eps_grad_offsets(L.ray_grad_offsets(n, n_max, S)[2] if self.ray_grad else n, n_max, eps.shape[-2])[2]
+        if self.gbuf.numel() < need:
+            self.gbuf = torch.zeros(need, device=dev)
+            self.grad = self.gbuf[:n]
+            self._xplan = None
+
+    def _latent_grad_finish(self, N, S):
+        """``self.d_eps`` of the step: the one set's gradient, the rows' - or, in netchunk mode, the pairs': the rows of a pair are one
+        contiguous segment of the step's rows, summed in a fixed order (no atomics: bit-reproducible like the blocks themselves)"""
+        acc, pairs = self._d_eps_acc, getattr(self, "_step_pairs", None)
+        if acc.dim() == 3 and pairs is not None:
+            idx = LT.netchunk_row_index(N, S, self.netchunk, self.chunk)
+            acc = LT.rows_to_pairs_sum(acc, torch.bincount(idx, minlength=pairs.shape[0]).tolist())
+        self.d_eps = acc
+
     def _pass(self, a, b, t_vals, t_rand, eps, S, flags, target, beta, scalars, entropy, d_ent, grad=None, accumulate=False, z_vals=None,
-              weights=None, depth=None, ray_grad=False):
+              weights=None, depth=None, ray_grad=False, latent_grad=False):
         """One pass over rows [a, b) of the packed rays into the persistent buffers: the fused forward (``t_rand`` / ``z_vals`` and the
         optional ``weights [N,S,K]`` output are per-ray too and sliced alike) and, given a ``grad`` buffer, a STASH forward followed by the
         KDE-NLL loss (+ ``beta`` * entropy; means over the step's whole shard) into ``scalars`` and the backward into ``grad``
@@ -326,7 +357,8 @@ class Trainer:
         if LT.check_rows(eps, self.packed.shape[0], "rays of the shard"):         # CFNERF_F_EPS_ROWS: the slice's rows
             eps, flags = eps[a:b], flags | L.F_EPS_ROWS
         L.check(lib.cfnerf_render_fwd(net.handle, L.ptr(self.packed[a:b]), L.ptr(t_vals), L.ptr(rows(t_rand)), L.ptr(rows(z_vals)), L.ptr(eps),
-                                      n, S, K, flags | (L.F_STASH if grad is not None else 0) | (L.F_RAY_GRAD if ray_grad else 0),
+                                      n, S, K, flags | (L.F_STASH if grad is not None else 0) | (L.F_RAY_GRAD if ray_grad else 0)
+                                      | (L.FLAG_EPS_GRAD if latent_grad and grad is not None else 0),
                                       L.ptr(self.rgb_map[a:b]), L.ptr(self.disp[a:b]),
                                       L.ptr(self.depth[a:b]), None, L.ptr(rows(weights)), None, None, L.ptr(entropy), st), "cfnerf_render_fwd")
         if grad is None:
@@ -361,6 +393,12 @@ class Trainer:
             r_off, z_off, _ = L.ray_grad_offsets(net.n_params, n, S)
             self.d_rays[a:b] = self.gbuf[r_off:r_off + n * 11].view(n, 11)
             self.d_z[a:b] = self.gbuf[z_off:z_off + n * S].view(n, S)
+        if latent_grad:                         # the pass's latent blocks (per-launch quantities too) -> the step's sum / the step's rows
+            e_off, er_off, _ = L.eps_grad_offsets(L.ray_grad_offsets(net.n_params, n, S)[2] if ray_grad else net.n_params, n, K)
+            if eps.dim() == 3:
+                self._d_eps_acc[a:b] = self.gbuf[er_off:er_off + n * K * 4].view(n, K, 4)
+            else:
+                self._d_eps_acc += self.gbuf[e_off:e_off + K * 4].view(K, 4)
 
     def forward_backward(self, H, W, focal, rays, target, t_rand=None, eps=None, near=0., far=1., ndc=True,
                          lindisp=False, white_bkgd=False, perturb=1., t_vals=None, eps_chunks=None, depth_rays=None, target_depth=None,
@@ -395,6 +433,7 @@ class Trainer:
         if depth is not None:
             self._depth_buffers(depth[0], N, K)
         _pack_rays(H, W, focal, rays=rays, ndc=ndc, near=near, far=far, out=self.packed)
+        self._step_pairs = None
         if eps is None:
             if self.latent_draws == "netchunk" and eps_chunks is None and (self.world > 1 or self.force_allreduce):
                 raise RuntimeError("netchunk latents of a sharded step come from Trainer.step (or pass eps_chunks=)")
@@ -403,6 +442,7 @@ class Trainer:
             tr, eps, pairs = LT.train_latents(self.latent_draws, None if eps_chunks is None else _f32c(eps_chunks), N=N * self.world, S=S, K=K,
                                               netchunk=self.netchunk, chunk=self.chunk, perturb=perturb)
             t_rand = tr if t_rand is None else t_rand
+            self._step_pairs = pairs
             if pairs is not None:
                 self.last_eps_chunks = pairs                                # (the step's pairs: identical on every rank)
                 eps = eps[self.rank * N:(self.rank + 1) * N]
@@ -423,8 +463,13 @@ class Trainer:
         # One slice writes its scalars and entropy straight into the step's own buffers.
         if self.ray_grad:
             self._ray_grad_buffers(N, S, max(first, N - first) if first is not None else N // n_sl)
+        if self.latent_grad:
+            self._latent_grad_buffers(eps, S, max(first, N - first) if first is not None else N // n_sl)
         if first is not None:
-            return self._first_call_and_rest(first, N, t_vals, t_rand, eps, S, flags, target, depth, z_vals)
+            self._first_call_and_rest(first, N, t_vals, t_rand, eps, S, flags, target, depth, z_vals)
+            if self.latent_grad:
+                self._latent_grad_finish(N, S)
+            return self.grad
         Ns = N // n_sl
         net.ensure_workspace(Ns, S, K)
         if n_sl == 1:
@@ -438,7 +483,7 @@ class Trainer:
             sc_sum, ent_sum = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         for i in range(n_sl):
             self._pass(i * Ns, (i + 1) * Ns, t_vals, t_rand, eps, S, flags, target, self.beta1 / (self.world * n_sl), sc, ent, d_ent,
-                       grad=self.grad, accumulate=i > 0, depth=depth, ray_grad=self.ray_grad, z_vals=z_vals)
+                       grad=self.grad, accumulate=i > 0, depth=depth, ray_grad=self.ray_grad, latent_grad=self.latent_grad, z_vals=z_vals)
             if n_sl > 1:
                 sc_sum += sc
                 ent_sum += ent
@@ -446,6 +491,8 @@ class Trainer:
             self.scalars[:3] = sc_sum[:3]
             self.scalars[3] = -10.0 * torch.log10(sc_sum[2])                # HLP:16 on the batch's mse
             self.entropy.copy_(ent_sum / n_sl)
+        if self.latent_grad:
+            self._latent_grad_finish(N, S)
         return self.grad
 
     def _first_call_and_rest(self, first, N, t_vals, t_rand, eps, S, flags, target, depth, z_vals=None):
@@ -456,9 +503,9 @@ class Trainer:
         self.net.ensure_workspace(max(first, N - first), S, self.net.K_samples)
         sc, ent = torch.zeros(4, device=dev), torch.zeros(1, device=dev)
         self._pass(0, first, t_vals, t_rand, eps, S, flags, target, self.beta1, self.scalars, self.entropy, self.d_ent, grad=self.grad,
-                   depth=depth, ray_grad=self.ray_grad, z_vals=z_vals)
+                   depth=depth, ray_grad=self.ray_grad, latent_grad=self.latent_grad, z_vals=z_vals)
         self._pass(first, N, t_vals, t_rand, eps, S, flags, target, 0.0, sc, ent, None, grad=self.grad, accumulate=True, depth=depth,
-                   ray_grad=self.ray_grad, z_vals=z_vals)
+                   ray_grad=self.ray_grad, latent_grad=self.latent_grad, z_vals=z_vals)
         sc[:3] += self.scalars[:3]
         self.scalars[:3] = sc[:3]
         self.scalars[3] = -10.0 * torch.log10(sc[2])                        # HLP:16 on the batch's mse
@@ -519,6 +566,10 @@ class Trainer:
         loss_fine + loss_coarse.  Returns it; ``self.scalars`` holds the fine pass's [loss, nll, mse, psnr]."""
         if self.latent_draws == "netchunk":
             raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
+        if self.latent_grad:
+            raise NotImplementedError("Trainer(latent_grad=True) is not supported by forward_backward_hierarchical / step_hierarchical: the latent "
+                                      "blocks of CFNERF_F_EPS_GRAD are sized and collected by forward_backward / step alone (the fine pass under "
+                                      "autograd, render_rays(hierarchical_extension=True), gives eps.grad)")
         if depth_rays is not None or target_depth is not None:
             raise NotImplementedError("depth rays are not supported by the hierarchical-sampling extension")
         if _ignored.get("occupancy") is not None:
@@ -564,6 +615,9 @@ class Trainer:
         """One full train step of the coarse + fine EXTENSION (see forward_backward_hierarchical)."""
         if self.latent_draws == "netchunk":
             raise NotImplementedError("latent_draws='netchunk' is not supported by the hierarchical-sampling extension")
+        if self.latent_grad:
+            raise NotImplementedError("Trainer(latent_grad=True) is not supported by forward_backward_hierarchical / step_hierarchical "
+                                      "(refused before the step draws or launches anything; see forward_backward_hierarchical)")
         if kw.get("occupancy") is not None:
             raise NotImplementedError("occupancy= (sampling through an occupancy grid) is not supported by step_hierarchical: both choose "
                                       "the depths of the pass; use step(occupancy=)")

@@ -160,7 +160,7 @@ enum {
                                            call (the same bits); d_z_vals / d_rays_d by a second launch that reads raw once more, skipped when neither
                                            is wanted, as the first is when d_raw is not.  No atomics: bit-reproducible.  Every entry point that takes
                                            `flags` refuses the bit.  Without the bit the call is what it was */
-    CFNERF_F_CULL       = 0x800         /* (= 1 << 11, bit 11) render through an occupancy grid: samples in empty cells never reach the network.  An
+    CFNERF_F_CULL       = 0x800,        /* (= 1 << 11, bit 11) render through an occupancy grid: samples in empty cells never reach the network.  An
                                            EVALUATION path (inference only, no backward) over the unfused seam, with no new entry point:
                                              cfnerf_sample_points with the flag reads its `pts` ARGUMENT as a pointer to a HOST struct cfnerf_cull (below) -
                                                the caller passes (float*)&cull - and writes z_vals as always plus the keep / skip decision of every sample
@@ -174,6 +174,29 @@ enum {
                                            "nothing synchronises" contract of the train step does not cover this path and is not affected by it.  The
                                            compaction is deterministic (no atomics).  cfnerf_composite_bwd does not take the bit.  Every entry point that takes
                                            `flags` other than cfnerf_sample_points refuses it.  Without the bit every call is what it was */
+    CFNERF_F_EPS_GRAD   = 0x1000        /* (= 1 << 12, bit 12) the matching cfnerf_render_bwd / cfnerf_render_bwd_accumulate / cfnerf_network_bwd also writes
+                                           d loss / d eps, the gradient with respect to the latents (in the reference eps.mul(std).add_(mean), MOD:239,251,
+                                           is an ordinary autograd line: fitting a latent set to an observation, per-image or per-ray latents, a learned
+                                           base distribution in front of the flows).  Accepted by cfnerf_render_fwd and cfnerf_network_fwd, and only
+                                           together with CFNERF_F_STASH (the stash remembers it; the forward launch and every output bit are what they
+                                           are without it); combines with CFNERF_F_EPS_ROWS, CFNERF_F_RAY_GRAD, CFNERF_F_COTANGENTS, CFNERF_F_INPUT_GRAD,
+                                           CFNERF_F_LINDISP, CFNERF_F_WHITE_BKGD, z_vals_opt and both precision modes; refused with CFNERF_F_GEOMETRY,
+                                           CFNERF_F_KSTATS_EXT and CFNERF_F_CULL.  The backward of such a stash treats grad_flat as [er_off + n * K * 4]
+                                           floats, n = N rays (cfnerf_render_fwd) or P points (cfnerf_network_fwd).  With base_end the end of the blocks
+                                           the stash already asks for - param_count, z_off + N * S with CFNERF_F_RAY_GRAD, x_off + P * (input_ch +
+                                           input_ch_views) with CFNERF_F_INPUT_GRAD -
+                                               e_off = (base_end + 63) / 64 * 64,   er_off = e_off + (4 * K + 63) / 64 * 64 :
+                                           d_eps [K,4] from e_off and d_eps_rows [n,K,4] from er_off, columns rgb then alpha like eps; the pad floats are
+                                           not written; everything before e_off is bit for bit what it is without the flag.  d_eps_rows[i] is
+                                           d loss / d (row i of eps) had the launch been a CFNERF_F_EPS_ROWS launch - for a launch with one [K,4] set, the
+                                           rows launch with n identical rows.  d_eps is the sum of the rows over i in a fixed order (double accumulators,
+                                           rounded once): for a launch with one set, the gradient of that set.  Both hold the chain through
+                                           z0 = eps * std + mean and the direct term of the base log-normal in the entropy (MOD:268,283,286; over the
+                                           launch -d_entropy * eps[k,3] / K for the density latent and -d_entropy * eps[k,c] / (3 K) for a colour latent,
+                                           each row 1 / n of it with its own eps).  Both are per-launch quantities: ALWAYS overwritten, also by
+                                           cfnerf_render_bwd_accumulate.  No atomics: bit-reproducible.  cfnerf_workspace_bytes does not change - the
+                                           caller's grad_flat is the only new memory.  Every other entry point that takes flags refuses it.  Without the
+                                           flag there is no extra launch and every argument, buffer shape and output bit is what it was */
 };
 
 /* The cotangents of a CFNERF_F_COTANGENTS backward: a HOST struct of DEVICE pointers, passed in place of d_rgb_map. */
@@ -378,7 +401,9 @@ CFNERF_API uint64_t cfnerf_model_stash_generation(const cfnerf_model* m);
  * forward is differentiated with its per-ray rows, read from the caller's eps buffer (see CFNERF_F_EPS_ROWS).  If the forward carried
  * CFNERF_F_COTANGENTS, d_rgb_map is NOT a device array: it is (const float*)&cot of a host struct cfnerf_cotangents, which adds the cotangents of
  * disp_map, weights and raw (each may be NULL; see the flag).  If the forward carried CFNERF_F_RAY_GRAD, grad_flat is [z_off + N * S] floats and the call also
- * writes d_rays [N,11] from r_off and d_z [N,S] from z_off (layout and columns at CFNERF_F_RAY_GRAD); without it only [0, param_count) is touched. */
+ * writes d_rays [N,11] from r_off and d_z [N,S] from z_off (layout and columns at CFNERF_F_RAY_GRAD); without it only [0, param_count) is touched.
+ * If the forward carried CFNERF_F_EPS_GRAD, grad_flat is [er_off + N * K * 4] floats and the call also writes d_eps [K,4] from e_off and
+ * d_eps_rows [N,K,4] from er_off, behind those blocks (layout at CFNERF_F_EPS_GRAD); _accumulate overwrites these two as well. */
 CFNERF_API int cfnerf_render_bwd(cfnerf_model* m, uint64_t stash_generation, const float* d_rgb_map, const float* d_depth_map,
                       const float* d_entropy, float* grad_flat, cfnerf_stream s);
 /* replaces: the same loss.backward() when ONE optimiser step's batch is walked in slices (the reference renders any N_rand and any
@@ -404,7 +429,8 @@ CFNERF_API int cfnerf_render_bwd_accumulate(cfnerf_model* m, uint64_t stash_gene
  * [x_off + P * (input_ch + input_ch_views)] floats, x_off = (cfnerf_param_count(cfg) + 63) / 64 * 64: the parameter gradient in
  * [0, param_count) as before, and d_x [P, input_ch + input_ch_views] = d loss / d x row-major from x_off (exact-fp32 MFMA in both
  * precision modes, no atomics: bit-reproducible); the floats between param_count and x_off are not written.  Without that flag
- * only [0, param_count) is touched.                                                                                      */
+ * only [0, param_count) is touched.  If the forward carried CFNERF_F_EPS_GRAD, grad_flat is [er_off + P * K * 4] floats and the call also
+ * writes d_eps [K,4] from e_off and d_eps_rows [P,K,4] from er_off, behind the blocks above (layout at CFNERF_F_EPS_GRAD).    */
 CFNERF_API int cfnerf_network_bwd(cfnerf_model* m, uint64_t stash_generation, const float* d_raw, const float* d_entropy,
                        float* grad_flat, cfnerf_stream s);
 /* replaces: loss.backward() through raw2outputs(raw, z_vals, rays_d) RUN:411-454, stateless: the forward is recomputed from

@@ -5,7 +5,7 @@ A kernel is `same` when its instruction stream is identical after comments, .loc
 labels are stripped.  For a kernel that differs, the per-opcode counts of its floating-point instructions (v_*_f32, v_pk_*_f32,
 v_fma* / v_fmac*, v_exp / v_log / v_rcp / v_sqrt; the _e32 / _e64 encoding suffix ignored) are compared as well: `fp equal` means
 the arithmetic is the same and only its schedule or register allocation moved.
---changed NAME: the kernels (substring of the demangled name) that are ALLOWED to differ.  Exit status 1 when any other kernel
+--changed NAME: the kernels (substring of the demangled name) that are ALLOWED to differ or to be new.  Exit status 1 when any other kernel
 differs, appears or disappears, or when an allowed kernel's floating-point counts differ."""
 import re
 import subprocess
@@ -61,7 +61,7 @@ def main():
         ok = any(x in dem[n] for x in allowed)
         if n not in a or n not in b:
             print(f"{'only in ' + (args[0] if n in a else args[1]):28s} {dem[n]}")
-            bad += 1
+            bad += 0 if (ok and n in b) else 1          # (a NEW kernel named by --changed is expected)
         elif a[n] == b[n]:
             same += 1
         else:
