@@ -15,6 +15,15 @@ F_CULL = 0x800              # cfnerf_sample_points: pts is a Cull; cfnerf_compos
 # CFNERF_F_EPS_GRAD (cfnerf_render_fwd / cfnerf_network_fwd with F_STASH: the backward also writes d_eps and d_eps_rows, eps_grad_offsets).  Not an
 # ``F_`` name: tests/test_cull_cpu.py pins how many of those this module has
 FLAG_EPS_GRAD = 0x1000
+# CFNERF_F_RAY_REG (or-ed into the white_bkgd argument of cfnerf_composite_fwd: weights_opt is a RayReg).  Stored under a ``FLAG_`` name for the
+# same reason; ``F_RAY_REG`` resolves to it through the module's __getattr__ below, so it is spelled like the header's without being counted
+FLAG_RAY_REG = 0x2000
+
+
+def __getattr__(name):
+    if name == "F_RAY_REG":
+        return FLAG_RAY_REG
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def input_grad_offset(n_params: int) -> int:
@@ -90,6 +99,22 @@ class SparseRaw(C.Structure):
     """cfnerf_sparse_raw of include/cfnerf.h: where the rows of a CFNERF_F_CULL cfnerf_composite_fwd's raw belong, passed in place of
     weights_opt (``struct_arg``)"""
     _fields_ = [("slot", C.c_void_p), ("ray_start", C.c_void_p), ("weights_opt", C.c_void_p)]
+
+
+class RayReg(C.Structure):
+    """cfnerf_ray_reg of include/cfnerf.h: the inputs and outputs of a CFNERF_F_RAY_REG cfnerf_composite_fwd, passed in place of weights_opt
+    (``struct_arg``)"""
+    _fields_ = [("weights", C.c_void_p), ("rays", C.c_void_p), ("lambda_dist", C.c_float), ("lambda_ent", C.c_float), ("acc_min", C.c_float),
+                ("n_total", C.c_int64), ("d_weights", C.c_void_p), ("d_z_opt", C.c_void_p), ("scalars_out", C.c_void_p)]
+
+
+def ray_reg(weights, z_vals, d_weights, scalars_out, rays=None, d_z=None, lambda_dist=0.0, lambda_ent=0.0, acc_min=0.1, n_total=0, stream_=None):
+    """One CFNERF_F_RAY_REG launch on contiguous fp32 device tensors: weights [N,S,K], z_vals [N,S], rays [N,11] or None; writes d_weights [N,S,K],
+    d_z [N,S] (or None) and the 8 floats of scalars_out ({reg, dist, ent, frac} first).  Nothing synchronises."""
+    N, S, K = weights.shape
+    rr = RayReg(dptr(weights), dptr(rays), lambda_dist, lambda_ent, acc_min, int(n_total), dptr(d_weights), dptr(d_z), dptr(scalars_out))
+    check(lib().cfnerf_composite_fwd(None, ptr(z_vals), None, N, S, K, FLAG_RAY_REG, None, None, None, struct_arg(rr),
+                                     stream() if stream_ is None else stream_), "cfnerf_composite_fwd(CFNERF_F_RAY_REG)")
 
 
 def struct_arg(st):

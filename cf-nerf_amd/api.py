@@ -931,6 +931,61 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
 
 
 # --------------------------------------------------------------------------------------------
+class _RayRegFn(torch.autograd.Function):
+    """The ray regularisers as an autograd node over ONE CFNERF_F_RAY_REG launch: the forward keeps the kernel's (scaled) ``d_weights`` and,
+    when ``z_vals`` asks for a gradient, its direct ``d_z``; the backward multiplies them by the incoming cotangent.  Output: the launch's
+    8 scalars, ``[0]`` = reg - the one entry whose cotangent is read."""
+
+    @staticmethod
+    def forward(ctx, weights, z_vals, rays, lambda_dist, lambda_ent, acc_min, n_total):
+        w, z = _f32c(weights), _f32c(z_vals)
+        want_z = ctx.needs_input_grad[1]
+        d_w, d_z = torch.empty_like(w), (torch.empty_like(z) if want_z else None)
+        out = torch.empty(8, device=w.device)
+        L.ray_reg(w, z, d_w, out, rays=rays, d_z=d_z, lambda_dist=lambda_dist, lambda_ent=lambda_ent, acc_min=acc_min, n_total=n_total)
+        ctx.d_w, ctx.d_z = d_w, d_z
+        ctx.dtypes = (weights.dtype, z_vals.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        g = d_out[0]
+        d_w = (ctx.d_w * g).to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
+        d_z = (ctx.d_z * g).to(ctx.dtypes[1]) if ctx.d_z is not None else None
+        return d_w, d_z, None, None, None, None, None
+
+
+def ray_regularizers(weights, z_vals, rays=None, distortion=0., entropy=0., acc_min=0.1, n_total=None):
+    """The two ray regularisers of few-view training on the composite's ``weights [N,S,K]`` (``render_rays(retweights=True)`` on the fused
+    path, ``raw2outputs`` on the seam) and the depths ``z_vals [N,S]``, in ONE launch (CFNERF_F_RAY_REG, include/cfnerf.h has the formulas):
+    ``reg = distortion * dist + entropy * ent`` with ``dist`` the distortion loss of mip-NeRF 360 on the intervals' normalised midpoints,
+    ``ent`` the ray entropy of InfoNeRF over the (ray, latent) pairs whose weights sum above ``acc_min``, both means over ``n_total``
+    (default N) rays and the K latents.  ``rays``: the packed ``ray_batch [N,11]`` or ``(near, far)`` - the depths are normalised to
+    ``(z - near) / (far - near)``; None: taken as they are.  A weight of 0 skips that term.
+
+    Returns ``(reg, parts)``: ``reg`` a 0-dim tensor on the graph - ``weights.grad`` and, when ``z_vals`` requires grad, the direct
+    ``z_vals.grad`` (the path through the weights is the composite's own backward) - and ``parts = {'dist', 'ent', 'frac'}``, 0-dim
+    tensors off the graph (``frac``: the fraction of pairs above ``acc_min``).  Nothing synchronises with the host."""
+    _need_gpu(weights, "weights")
+    if weights.dim() != 3 or z_vals.dim() != 2 or tuple(z_vals.shape) != tuple(weights.shape[:2]):
+        raise ValueError(f"weights must be [N,S,K] and z_vals [N,S], got {tuple(weights.shape)} and {tuple(z_vals.shape)}")
+    N = weights.shape[0]
+    if rays is not None:
+        if isinstance(rays, (tuple, list)):
+            near, far = rays
+            packed = torch.zeros(N, 11, device=weights.device)
+            packed[:, 6] = torch.as_tensor(near, dtype=torch.float32, device=weights.device).reshape(-1)
+            packed[:, 7] = torch.as_tensor(far, dtype=torch.float32, device=weights.device).reshape(-1)
+            rays = packed
+        else:
+            rays = _f32c(rays)
+            if rays.dim() != 2 or tuple(rays.shape) != (N, 11):
+                raise ValueError(f"rays must be the packed ray_batch [N,11] or (near, far), got {tuple(rays.shape)}")
+    out = _RayRegFn.apply(weights, z_vals.to(weights.device), rays, float(distortion), float(entropy), float(acc_min), int(n_total or 0))
+    parts = out.detach()
+    return out[0], {'dist': parts[1], 'ent': parts[2], 'frac': parts[3]}
+
+
 def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True, raw=False, weights=False, pts=False, kstats=False,
                 entropy=True):
     """cfnerf_render_fwd of the packed ``rays [N,11]`` into newly allocated outputs.  Returns a dict with ``rgb_map [N,3,K]``,

@@ -157,7 +157,8 @@ static int check_device(const cfnerf_model* m) {
 // CFNERF_F_COTANGENTS makes the backward of a cfnerf_render_fwd stash read its d_rgb_map argument as a host cfnerf_cotangents,
 // CFNERF_F_SEAM_GRAD belongs to the white_bkgd argument of cfnerf_composite_bwd alone, CFNERF_F_CULL turns the pts argument of
 // cfnerf_sample_points into a host cfnerf_cull (and travels in the white_bkgd argument of cfnerf_composite_fwd), CFNERF_F_EPS_GRAD asks the
-// backward of a cfnerf_render_fwd / cfnerf_network_fwd stash for d loss / d eps.
+// backward of a cfnerf_render_fwd / cfnerf_network_fwd stash for d loss / d eps, CFNERF_F_RAY_REG belongs to the white_bkgd argument of
+// cfnerf_composite_fwd alone (the ray regularisers of a cfnerf_ray_reg).
 // Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
@@ -176,6 +177,8 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_CULL (the occupancy-grid descriptor of cfnerf_sample_points; cfnerf_composite_fwd takes the bit in its white_bkgd argument)", who);
     if (flags & CFNERF_F_EPS_GRAD & ~allowed)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_EPS_GRAD (the latent gradient of cfnerf_render_fwd / cfnerf_network_fwd with CFNERF_F_STASH, written by their backward)", who);
+    if (flags & CFNERF_F_RAY_REG)                       // (no entry point with a `flags` argument takes it)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_RAY_REG (the ray regularisers of cfnerf_composite_fwd, passed in its white_bkgd argument)", who);
     return CFNERF_OK;
 }
 
@@ -200,6 +203,39 @@ static int check_geometry_flags(int flags) {
     for (const auto& b : bad)
         if (flags & b.bit)
             return fail(CFNERF_E_INVALID, "CFNERF_F_GEOMETRY is an eval-branch launch without the colour branch: it cannot be combined with %s", b.name);
+    return CFNERF_OK;
+}
+
+// CFNERF_F_RAY_REG in the white_bkgd argument of cfnerf_composite_fwd: everything is checked by name before anything touches a device
+static int composite_ray_reg(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K, int white_bkgd, const float* rgb_map,
+                             const float* disp_map, const float* depth_map, const cfnerf_ray_reg* rr, hipStream_t st) {
+    if (white_bkgd & CFNERF_F_CULL)
+        return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG cannot be combined with CFNERF_F_CULL (the regularisers read a dense weights [N,S,K])");
+    if (!rr) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: the weights_opt argument must be (float*)&rr of a host struct cfnerf_ray_reg, got NULL");
+    const struct { const void* p; const char* name; } banned[] = {{raw, "raw"}, {rays_d, "rays_d"}, {rgb_map, "rgb_map"}, {disp_map, "disp_map"},
+                                                                  {depth_map, "depth_map"}};
+    for (const auto& b : banned)
+        if (b.p) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: the %s argument must be NULL (nothing is composited)", b.name);
+    if (!z_vals) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: the z_vals argument is NULL");
+    if (!rr->weights) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: member weights of cfnerf_ray_reg is NULL");
+    if (!rr->d_weights) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: member d_weights of cfnerf_ray_reg is NULL");
+    if (!rr->scalars_out) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: member scalars_out of cfnerf_ray_reg is NULL");
+    if (reinterpret_cast<uintptr_t>(rr->scalars_out) % 8)
+        return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: member scalars_out of cfnerf_ray_reg must be 8-byte aligned");
+    if (S < 1) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: S must be at least 1, got %d", S);
+    if (K < 1) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: K must be at least 1, got %d", K);
+    if (N < 0) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: N must not be negative, got %lld", (long long)N);
+    if (S > 4096 || K > kMaxK) return fail(CFNERF_E_UNSUPPORTED, "CFNERF_F_RAY_REG: S must be in [1,4096] and K in [1,%d], got S=%d K=%d", kMaxK, S, K);
+    if (rr->n_total < 0) return fail(CFNERF_E_INVALID, "CFNERF_F_RAY_REG: member n_total of cfnerf_ray_reg is negative");
+    const int64_t n_total = rr->n_total ? rr->n_total : N;
+    RayRegArgs a{};
+    a.w = rr->weights; a.z = z_vals; a.rays = rr->rays; a.dw = rr->d_weights; a.dz = rr->d_z_opt; a.scalars = rr->scalars_out;
+    a.acc = reinterpret_cast<unsigned long long*>(rr->scalars_out + 2);
+    a.N = N; a.S = S; a.K = K;
+    a.inv = n_total > 0 ? 1.0 / ((double)n_total * K) : 0.0;
+    a.cd = (float)((double)rr->lambda_dist * a.inv); a.ce = (float)((double)rr->lambda_ent * a.inv);
+    a.lambda_dist = rr->lambda_dist; a.lambda_ent = rr->lambda_ent; a.acc_min = rr->acc_min;
+    HIPCHK(launch_ray_reg(a, st));
     return CFNERF_OK;
 }
 
@@ -480,6 +516,9 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
 int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K,
                          int white_bkgd, float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
                          cfnerf_stream s) {
+    if (white_bkgd & CFNERF_F_RAY_REG)           // nothing is composited: weights_opt is a host cfnerf_ray_reg
+        return composite_ray_reg(raw, z_vals, rays_d, N, S, K, white_bkgd, rgb_map, disp_map, depth_map,
+                                 reinterpret_cast<const cfnerf_ray_reg*>(weights_opt), (hipStream_t)s);
     if (white_bkgd & CFNERF_F_CULL) {            // raw is [P',K,4], weights_opt a host cfnerf_sparse_raw; white iff (white_bkgd & ~0x800) != 0
         const cfnerf_sparse_raw* sp = reinterpret_cast<const cfnerf_sparse_raw*>(weights_opt);
         if (!sp) return fail(CFNERF_E_INVALID, "CFNERF_F_CULL: the weights_opt argument must be (float*)&sp of a host struct cfnerf_sparse_raw, got NULL");

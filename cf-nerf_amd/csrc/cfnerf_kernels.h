@@ -86,6 +86,19 @@ struct CullArgs {
 hipError_t launch_cull(const CullArgs& a, hipStream_t st);      // count, scan, emit
 hipError_t launch_composite_sparse(const float* raw_c, const int32_t* slot, const int64_t* ray_start, const float* z, const float* d, int64_t N,
                                    int S, int K, int wb, float* rgb, float* disp, float* depth, float* weights, hipStream_t st);
+// CFNERF_F_RAY_REG (cfnerf_rayreg.hip): distortion + ray entropy of weights [N,S,K] and their gradient, from a cfnerf_ray_reg
+struct RayRegArgs {
+    const float *w, *z, *rays;      // [N,S,K] [N,S] [N,11] or null
+    float *dw, *dz;                 // [N,S,K]; [N,S] or null
+    float* scalars;                 // 8 floats, 8-byte aligned: {reg, dist, ent, frac}
+    unsigned long long* acc;        // three 64-bit accumulators in bytes 8..31 of `scalars`
+    int64_t N;
+    int32_t S, K;
+    float cd, ce;                   // lambda / (n_total K): the scale of each term's gradient; 0 skips the term
+    float lambda_dist, lambda_ent, acc_min;
+    double inv;                     // 1 / (n_total K)
+};
+hipError_t launch_ray_reg(const RayRegArgs& a, hipStream_t st);      // zeroes the accumulators, then one launch
 hipError_t launch_pack_index(const PackDesc* descs, int ndesc, uint32_t total, uint32_t* table /*[total][3]*/, hipStream_t st);      // once per model
 hipError_t launch_pack(const float* flat, float* packed, void* packed16, const uint32_t* table, uint32_t total, hipStream_t st);
 

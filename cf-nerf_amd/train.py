@@ -113,11 +113,18 @@ class Trainer:
     WHOLE loss, summed over the slices of a sliced step (CFNERF_F_EPS_GRAD): ``[K,4]`` for one latent set, ``[C,K,4]`` - one per pair, in
     draw order - in netchunk mode, ``[N,K,4]`` for explicit per-ray rows; columns rgb then alpha, like the latents.  The default changes
     nothing: same buffers, same launches.  ``forward_backward_hierarchical`` / ``step_hierarchical`` refuse the option (their passes never
-    carry the flag: the blocks behind the parameter gradient are sized by ``forward_backward`` alone)."""
+    carry the flag: the blocks behind the parameter gradient are sized by ``forward_backward`` alone).
+
+    ``distortion_lambda`` / ``ray_entropy_lambda`` > 0: the step's loss gains ``api.ray_regularizers`` of every ray of the launch (depth
+    rays included; means over the step's rays of all ranks; ``ray_entropy_acc_min`` is its ``acc_min``) - the distortion loss of mip-NeRF 360
+    and the ray entropy of InfoNeRF on the composite's weights.  ``self.scalars[0]`` includes the term and ``self.reg_scalars`` holds
+    ``[reg, dist, ent, frac]`` of the step; with ``ray_grad`` the direct gradient in the depths is added to ``self.d_z``.  Works with slices,
+    depth rays, ``occupancy=`` (the warped depths), netchunk latents and both precisions; the hierarchical extension refuses it.  With both
+    at 0 (the default) a step launches what it launched and writes the bits it wrote."""
 
     def __init__(self, net, lrate=5e-4, lrate_decay=250, beta1=0.0, world_size=1, group=None, start=0, force_allreduce=False,
                  overlap_comm=False, time_comm=False, max_rays_per_launch=None, latent_draws="launch", netchunk=1024 * 64, chunk=1024 * 32,
-                 depth_lambda=0.0, ray_grad=False, latent_grad=False):
+                 depth_lambda=0.0, ray_grad=False, latent_grad=False, distortion_lambda=0.0, ray_entropy_lambda=0.0, ray_entropy_acc_min=0.1):
         if latent_draws not in LT.LATENT_DRAWS:
             raise ValueError(f"latent_draws must be one of {LT.LATENT_DRAWS}, got {latent_draws!r}")
         if ray_grad and (int(world_size) > 1 or force_allreduce):
@@ -126,8 +133,15 @@ class Trainer:
         if latent_grad and (int(world_size) > 1 or force_allreduce):
             raise NotImplementedError("Trainer(latent_grad=True) with world_size > 1 / force_allreduce: the latent blocks of CFNERF_F_EPS_GRAD lie behind "
                                       "the parameter gradient in the buffer whose tail the gradient exchange uses for the next step's latents")
+        if distortion_lambda < 0 or ray_entropy_lambda < 0:
+            raise ValueError("distortion_lambda and ray_entropy_lambda must not be negative")
         self.ray_grad = bool(ray_grad)
         self.d_rays = self.d_z = None
+        # the ray regularisers (CFNERF_F_RAY_REG): weights of the two terms, and whether a pass runs them at all
+        self.distortion_lambda, self.ray_entropy_lambda = float(distortion_lambda), float(ray_entropy_lambda)
+        self.ray_entropy_acc_min = float(ray_entropy_acc_min)
+        self._reg = self.distortion_lambda > 0.0 or self.ray_entropy_lambda > 0.0
+        self._reg_n = None
         self.latent_grad = bool(latent_grad)
         self.d_eps = None
         self.latent_draws, self.netchunk, self.chunk = latent_draws, int(netchunk), (int(chunk) if chunk else None)
@@ -163,6 +177,8 @@ class Trainer:
         self.depth_lambda = float(depth_lambda)
         self.depth_loss = torch.zeros(1, device=dev)
         self._d_depth_n = None
+        # [reg, dist, ent, frac] of the step's ray regularisers on the local shard (contributions: means over the step's rays of all ranks)
+        self.reg_scalars = torch.zeros(4, device=dev)
         self.t = 0
         self._buf_n = None
         self._eps_rows = None           # this step's latent rows (netchunk mode): the stash reads them until the backward
@@ -324,6 +340,25 @@ class Trainer:
             self.grad = self.gbuf[:self.net.n_params]
             self._xplan = None
 
+    def _reg_buffers(self, N, S, K, z_vals, t_vals, t_rand, lindisp):
+        """The persistent buffers of a step with ray regularisers - the forward's ``weights`` and their cotangent ``[N,S,K]``, the launch's
+        8 scalars, the direct ``d_z`` with ``ray_grad`` - and the step's depths: the explicit ``z_vals``, else what the fused forward
+        samples for ``t_vals`` / ``t_rand`` / ``lindisp`` (cfnerf_sample_points: the same lines)"""
+        dev = self.net.flat.device
+        if self._reg_n != (N, S, K):
+            self._reg_w, self._reg_dw = torch.empty(N, S, K, device=dev), torch.empty(N, S, K, device=dev)
+            self._reg_sc = torch.zeros(8, device=dev)
+            self._reg_zbuf = torch.empty(N, S, device=dev)
+            self._reg_dz = torch.empty(N, S, device=dev) if self.ray_grad else None
+            self._reg_n = (N, S, K)
+        self.reg_scalars.zero_()
+        if z_vals is not None:
+            self._reg_z = z_vals
+        else:
+            L.check(L.lib().cfnerf_sample_points(L.ptr(self.packed), L.ptr(t_vals), L.ptr(t_rand), L.F_LINDISP if lindisp else 0, N, S,
+                                                 L.ptr(self._reg_zbuf), None, L.stream()), "cfnerf_sample_points")
+            self._reg_z = self._reg_zbuf
+
     def _latent_grad_buffers(self, eps, S, n_max):
         """The step's latent gradient, zeroed (``[K,4]`` or one row per ray), and the gradient buffer grown to hold the latent blocks of its
         largest pass (``n_max`` rays) behind the parameter gradient and the ray blocks (cfnerf.h, CFNERF_F_EPS_GRAD)"""
@@ -350,8 +385,14 @@ class Trainer:
         optional ``weights [N,S,K]`` output are per-ray too and sliced alike) and, given a ``grad`` buffer, a STASH forward followed by the
         KDE-NLL loss (+ ``beta`` * entropy; means over the step's whole shard) into ``scalars`` and the backward into ``grad``
         (``accumulate``: added to what it holds).  ``depth = (n_colour, target_depth)``: rows from ``n_colour`` on are depth rays - the
-        loss runs on the pass's colour rows, depth_term on its depth rows, and the backward gets ``d_depth_map``."""
+        loss runs on the pass's colour rows, depth_term on its depth rows, and the backward gets ``d_depth_map``.
+        With ray regularisers (``distortion_lambda`` / ``ray_entropy_lambda``) the stash carries CFNERF_F_COTANGENTS, the forward also writes
+        the pass's rows of the persistent ``weights``, one CFNERF_F_RAY_REG launch turns them into ``reg`` (added to ``scalars[0]`` and
+        ``self.reg_scalars``) and ``d_weights``, and the backward takes a cotangent descriptor."""
         net, lib, st = self.net, L.lib(), L.stream()
+        reg = self._reg and grad is not None
+        if reg:
+            weights, flags = self._reg_w, flags | L.F_COTANGENTS
         rows = lambda t: t[a:b] if t is not None else None
         n, K = b - a, net.K_samples
         if LT.check_rows(eps, self.packed.shape[0], "rays of the shard"):         # CFNERF_F_EPS_ROWS: the slice's rows
@@ -385,14 +426,25 @@ class Trainer:
                 scalars[0:1] += part
                 self.depth_loss += part / self.depth_lambda
                 d_depth = self.d_depth[a:b]
+        d_rgb_arg = L.ptr(self.d_rgb[a:b])
+        if reg:                                 # every ray of the launch, depth rays included; means over the step's rays of all ranks
+            L.ray_reg(self._reg_w[a:b], self._reg_z[a:b], self._reg_dw[a:b], self._reg_sc, rays=self.packed[a:b],
+                      d_z=self._reg_dz[a:b] if ray_grad else None, lambda_dist=self.distortion_lambda, lambda_ent=self.ray_entropy_lambda,
+                      acc_min=self.ray_entropy_acc_min, n_total=self.packed.shape[0] * self.world, stream_=st)
+            scalars[0:1] += self._reg_sc[0:1]
+            self.reg_scalars += self._reg_sc[:4]
+            cot = L.cotangents(self.d_rgb[a:b], None, self._reg_dw[a:b], None)
+            d_rgb_arg = L.cotangents_arg(cot)
         gen = lib.cfnerf_model_stash_generation(net.handle)
         bwd = lib.cfnerf_render_bwd_accumulate if accumulate else lib.cfnerf_render_bwd
-        L.check(bwd(net.handle, gen, L.ptr(self.d_rgb[a:b]), L.ptr(d_depth), L.ptr(d_ent) if self.beta1 and d_ent is not None else None,
+        L.check(bwd(net.handle, gen, d_rgb_arg, L.ptr(d_depth), L.ptr(d_ent) if self.beta1 and d_ent is not None else None,
                     L.ptr(grad), st), "cfnerf_render_bwd_accumulate" if accumulate else "cfnerf_render_bwd")
         if ray_grad:                            # the pass's ray blocks (per-launch quantities: the next pass overwrites them) -> the step's rows
             r_off, z_off, _ = L.ray_grad_offsets(net.n_params, n, S)
             self.d_rays[a:b] = self.gbuf[r_off:r_off + n * 11].view(n, 11)
             self.d_z[a:b] = self.gbuf[z_off:z_off + n * S].view(n, S)
+            if reg:                             # + the regularisers' direct gradient in the depths (the path through the weights is in the block)
+                self.d_z[a:b] += self._reg_dz[a:b]
         if latent_grad:                         # the pass's latent blocks (per-launch quantities too) -> the step's sum / the step's rows
             e_off, er_off, _ = L.eps_grad_offsets(L.ray_grad_offsets(net.n_params, n, S)[2] if ray_grad else net.n_params, n, K)
             if eps.dim() == 3:
@@ -454,6 +506,8 @@ class Trainer:
             w = warp_z_vals(self.packed, occupancy, t_vals, t_rand, lindisp)
             self.z_vals, self.n_occ = w['z_vals'], w['n_occ']
             z_vals, t_rand = self.z_vals, None
+        if self._reg:
+            self._reg_buffers(N, S, K, z_vals, t_vals, t_rand, lindisp)
         net._sync()
         flags = L.F_TRAIN | (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0)
         n_sl = self.n_slices(N)
@@ -572,6 +626,9 @@ class Trainer:
                                       "autograd, render_rays(hierarchical_extension=True), gives eps.grad)")
         if depth_rays is not None or target_depth is not None:
             raise NotImplementedError("depth rays are not supported by the hierarchical-sampling extension")
+        if self._reg:
+            raise NotImplementedError("Trainer(distortion_lambda= / ray_entropy_lambda=) is not supported by forward_backward_hierarchical / "
+                                      "step_hierarchical: the ray regularisers run on the passes of forward_backward / step alone")
         if _ignored.get("occupancy") is not None:
             raise NotImplementedError("occupancy= (sampling through an occupancy grid) is not supported by forward_backward_hierarchical / "
                                       "step_hierarchical: both choose the depths of the pass; use step(occupancy=)")
@@ -621,6 +678,9 @@ class Trainer:
         if kw.get("occupancy") is not None:
             raise NotImplementedError("occupancy= (sampling through an occupancy grid) is not supported by step_hierarchical: both choose "
                                       "the depths of the pass; use step(occupancy=)")
+        if self._reg:
+            raise NotImplementedError("Trainer(distortion_lambda= / ray_entropy_lambda=) is not supported by step_hierarchical "
+                                      "(refused before the step draws or launches anything; see forward_backward_hierarchical)")
         # always the plain one-bucket all-reduce: this gradient is grad_fine + grad_c, added by torch after the last backward, while
         # the early-range event that overlap_comm's first bucket waits for fires inside that backward, before the add
         return self._step(self.forward_backward_hierarchical, lambda: allreduce_sum_(self.gbuf, self.world, self.group, self.force_allreduce),

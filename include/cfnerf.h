@@ -174,7 +174,7 @@ enum {
                                            "nothing synchronises" contract of the train step does not cover this path and is not affected by it.  The
                                            compaction is deterministic (no atomics).  cfnerf_composite_bwd does not take the bit.  Every entry point that takes
                                            `flags` other than cfnerf_sample_points refuses it.  Without the bit every call is what it was */
-    CFNERF_F_EPS_GRAD   = 0x1000        /* (= 1 << 12, bit 12) the matching cfnerf_render_bwd / cfnerf_render_bwd_accumulate / cfnerf_network_bwd also writes
+    CFNERF_F_EPS_GRAD   = 0x1000,       /* (= 1 << 12, bit 12) the matching cfnerf_render_bwd / cfnerf_render_bwd_accumulate / cfnerf_network_bwd also writes
                                            d loss / d eps, the gradient with respect to the latents (in the reference eps.mul(std).add_(mean), MOD:239,251,
                                            is an ordinary autograd line: fitting a latent set to an observation, per-image or per-ray latents, a learned
                                            base distribution in front of the flows).  Accepted by cfnerf_render_fwd and cfnerf_network_fwd, and only
@@ -197,6 +197,32 @@ enum {
                                            cfnerf_render_bwd_accumulate.  No atomics: bit-reproducible.  cfnerf_workspace_bytes does not change - the
                                            caller's grad_flat is the only new memory.  Every other entry point that takes flags refuses it.  Without the
                                            flag there is no extra launch and every argument, buffer shape and output bit is what it was */
+    CFNERF_F_RAY_REG    = 0x2000        /* (= 1 << 13, bit 13) the two ray regularisers of few-view training as ONE stateless launch over the composite's
+                                           weights [N,S,K] (what CFNERF_F_COTANGENTS made differentiable): the distortion loss of mip-NeRF 360 and the
+                                           ray-entropy loss of InfoNeRF, with their gradient.  There is no new entry point: the bit is or-ed into the
+                                           `white_bkgd` ARGUMENT of cfnerf_composite_fwd, which then composites nothing - z_vals [N,S] (non-decreasing
+                                           per ray) is required, raw, rays_d, rgb_map, disp_map and depth_map must be NULL, and the `weights_opt` ARGUMENT
+                                           is read as a pointer to a HOST struct cfnerf_ray_reg (below), (float*)&rr; the struct is read during the call
+                                           and not kept.  For one (ray, latent), w_i = weights[n,i,k]:
+                                             s_i = (z_i - near) / (far - near), near / far = columns 6 / 7 of rays [N,11]; rays NULL: s_i = z_i
+                                             interval i < S-1 is [s_i, s_i+1]: m_i = (s_i + s_i+1) / 2, delta_i = s_i+1 - s_i; the last sample (the
+                                               composite's 1e10 interval) is the point m_S-1 = s_S-1, delta_S-1 = 0
+                                             D = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 delta_i
+                                             A = sum_i w_i,  p_i = w_i / (A + 1e-10),  H = - sum_i p_i log(p_i + 1e-10),  mask = (A > acc_min), a constant
+                                           and over the launch, with n = n_total (0: N):
+                                             dist = sum_nk D / (n K),  ent = sum_nk mask H / (n K),  frac = sum_nk mask / (n K),
+                                             reg = lambda_dist dist + lambda_ent ent
+                                           scalars_out receives {reg, dist, ent, frac} (+ 4 floats of zeros), d_weights [N,S,K] = d reg / d weights -
+                                           scaled, a cfnerf_cotangents.d_weights as it stands - and d_z_opt [N,S], when given, the DIRECT d reg / d z_vals
+                                           through m and delta, summed over K, divided by (far - near); the path through the weights is the composite's
+                                           backward's.  Launches that share n_total add up: their scalars and gradients are those of slices of one batch.
+                                           O(S) per (ray, latent); any S in [1, 4096], K in [1, 128], N >= 0.  A lambda of 0 skips that term: the gradient
+                                           then has the bits of the other term's alone.  The sums are integer accumulations: bit-reproducible.  Refused by
+                                           name, before anything touches a device: a NULL struct, a NULL weights / d_weights / scalars_out / z_vals, a
+                                           non-NULL raw / rays_d / rgb_map / disp_map / depth_map, the bit together with CFNERF_F_CULL, S < 1, K < 1, N < 0.
+                                           cfnerf_composite_bwd does not take the bit; every entry point that takes `flags` refuses it.  NOTE: a white_bkgd
+                                           value with bit 13 set used to mean "white" like any non-zero value; it now selects this mode (nothing in the
+                                           project passes such a value).  Without the bit every call is what it was */
 };
 
 /* The cotangents of a CFNERF_F_COTANGENTS backward: a HOST struct of DEVICE pointers, passed in place of d_rgb_map. */
@@ -237,6 +263,21 @@ typedef struct cfnerf_sparse_raw {
     const int64_t* ray_start;           /* [N+1] */
     float* weights_opt;                 /* [N,S,K] or NULL; a culled sample's weights are written as 0 */
 } cfnerf_sparse_raw;
+
+/* The inputs and outputs of a CFNERF_F_RAY_REG cfnerf_composite_fwd: a HOST struct of DEVICE pointers, passed in place of weights_opt;
+ * read during the call, not kept. */
+typedef struct cfnerf_ray_reg {
+    const float* weights;               /* [N,S,K] required: weights_opt of a forward */
+    const float* rays;                  /* [N,11] or NULL: near / far in columns 6 / 7; NULL: s = z */
+    float   lambda_dist;                /* weight of the distortion term; 0 skips it */
+    float   lambda_ent;                 /* weight of the ray-entropy term; 0 skips it */
+    float   acc_min;                    /* a (ray, latent) enters the entropy iff its sum of weights is above this */
+    int64_t n_total;                    /* rays the means are taken over; 0 means N */
+    float*  d_weights;                  /* [N,S,K] out, required: d reg / d weights, scaled */
+    float*  d_z_opt;                    /* [N,S] out or NULL: the direct d reg / d z_vals */
+    float*  scalars_out;                /* 8 floats out, 8-byte aligned, required: {reg, dist, ent, frac, 0, 0, 0, 0}; the 32 bytes serve as the
+                                           launch's accumulators until it ends */
+} cfnerf_ray_reg;
 
 CFNERF_API int         cfnerf_version(void);
 CFNERF_API const char* cfnerf_last_error(void);
@@ -364,7 +405,9 @@ CFNERF_API int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* 
  * and the weights proper.  The maps and weights are, bit for bit, those of the plain call on the dense raw [N,S,K,4] in which every culled
  * sample has the density latent -1e4 (softplus gives exactly 0 there): a culled sample contributes alpha = 0.  Only the sign of slot is
  * read; a ray's rows are fetched through a descriptor of exactly its block [ray_start[ray], ray_start[ray + 1]), so inconsistent indices
- * read zeros, never another ray's rows.  A NULL struct, slot or ray_start is refused.  No backward: cfnerf_composite_bwd does not take the bit. */
+ * read zeros, never another ray's rows.  A NULL struct, slot or ray_start is refused.  No backward: cfnerf_composite_bwd does not take the bit.
+ * With CFNERF_F_RAY_REG or-ed into white_bkgd nothing is composited: the call evaluates the distortion and ray-entropy regularisers of
+ * weights [N,S,K] and their gradient, from (float*)&rr of a host struct cfnerf_ray_reg in weights_opt (contract at the flag). */
 CFNERF_API int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d,
                          int64_t N, int S, int K, int white_bkgd,
                          float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
