@@ -18,11 +18,15 @@ FLAG_EPS_GRAD = 0x1000
 # CFNERF_F_RAY_REG (or-ed into the white_bkgd argument of cfnerf_composite_fwd: weights_opt is a RayReg).  Stored under a ``FLAG_`` name for the
 # same reason; ``F_RAY_REG`` resolves to it through the module's __getattr__ below, so it is spelled like the header's without being counted
 FLAG_RAY_REG = 0x2000
+# CFNERF_F_KSCORES (or-ed into the white_bkgd argument of cfnerf_composite_fwd: weights_opt is a KScores); ``F_KSCORES`` resolves like ``F_RAY_REG``
+FLAG_KSCORES = 0x4000
 
 
 def __getattr__(name):
     if name == "F_RAY_REG":
         return FLAG_RAY_REG
+    if name == "F_KSCORES":
+        return FLAG_KSCORES
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -115,6 +119,46 @@ def ray_reg(weights, z_vals, d_weights, scalars_out, rays=None, d_z=None, lambda
     rr = RayReg(dptr(weights), dptr(rays), lambda_dist, lambda_ent, acc_min, int(n_total), dptr(d_weights), dptr(d_z), dptr(scalars_out))
     check(lib().cfnerf_composite_fwd(None, ptr(z_vals), None, N, S, K, FLAG_RAY_REG, None, None, None, struct_arg(rr),
                                      stream() if stream_ is None else stream_), "cfnerf_composite_fwd(CFNERF_F_RAY_REG)")
+
+
+class KScores(C.Structure):
+    """cfnerf_kscores of include/cfnerf.h: the inputs and outputs of a CFNERF_F_KSCORES cfnerf_composite_fwd, passed in place of weights_opt
+    (``struct_arg``)"""
+    _fields_ = [("samples", C.c_void_p), ("target", C.c_void_p), ("sorted", C.c_void_p), ("quantiles", C.c_void_p), ("rank_code", C.c_void_p),
+                ("pit", C.c_void_p), ("crps", C.c_void_p), ("n_levels", C.c_int32), ("level_lo", C.c_int32 * 16), ("level_frac", C.c_float * 16)]
+
+
+def quantile_levels(levels, K):
+    """The ``(lo, frac)`` pairs of include/cfnerf.h (CFNERF_F_KSCORES) for quantile levels ``q`` in [0,1] of K samples: ``lo = floor(q (K-1))`` in
+    double, ``frac`` the fractional part rounded once to fp32 - the ``numpy.quantile(method="linear")`` position.  (A ``frac`` that rounds up
+    to 1.0f is the next order statistic.)"""
+    import math
+    import struct
+    out = []
+    for q in levels:
+        q = float(q)
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"a quantile level must lie in [0, 1], got {q!r}")
+        pos = q * (K - 1)
+        lo = int(math.floor(pos))
+        frac = struct.unpack("f", struct.pack("f", pos - lo))[0]
+        if frac >= 1.0:
+            lo, frac = lo + 1, 0.0
+        if lo >= K - 1:
+            lo, frac = K - 1, 0.0
+        out.append((lo, frac))
+    return out
+
+
+def k_scores(samples, M, K, target=None, sorted_out=None, quantiles=None, levels=(), rank_code=None, pit=None, crps=None, stream_=None):
+    """One CFNERF_F_KSCORES launch on contiguous device tensors: samples [M,K] fp32, target [M] or None; writes the outputs that are given
+    (sorted_out [M,K], quantiles [M,len(levels)], rank_code [M] int32, pit [M], crps [M]).  ``levels``: ``(lo, frac)`` pairs (``quantile_levels``).
+    Nothing synchronises."""
+    ks = KScores(dptr(samples), dptr(target), dptr(sorted_out), dptr(quantiles), dptr(rank_code), dptr(pit), dptr(crps), len(levels))
+    for t, (lo, frac) in enumerate(levels[:16]):
+        ks.level_lo[t], ks.level_frac[t] = lo, frac
+    check(lib().cfnerf_composite_fwd(None, None, None, M, 1, K, FLAG_KSCORES, None, None, None, struct_arg(ks),
+                                     stream() if stream_ is None else stream_), "cfnerf_composite_fwd(CFNERF_F_KSCORES)")
 
 
 def struct_arg(st):

@@ -986,6 +986,48 @@ def ray_regularizers(weights, z_vals, rays=None, distortion=0., entropy=0., acc_
     return out[0], {'dist': parts[1], 'ent': parts[2], 'frac': parts[3]}
 
 
+@torch.no_grad()
+def k_scores(samples, target=None, levels=None, return_sorted=False):
+    """The K latent samples ``samples [...,K]`` (fp32, on the GPU; K <= 128) scored as an ensemble, row by row, in ONE launch
+    (CFNERF_F_KSCORES, include/cfnerf.h has the definitions).  Returns a dict with
+
+    * ``quantiles [...,Q]`` at the ``levels`` (a sequence of at most 16 numbers in [0,1]; ``numpy.quantile(method="linear")``), when given;
+    * ``sorted [...,K]``, the samples ascending (a permutation of their bits; NaN last), with ``return_sorted``;
+    * with ``target [...]``: ``crps [...]`` (the CRPS of the K-member ensemble against the target), ``rank_code [...]`` int32
+      (``2 #{x_k < y} + #{x_k == y}``) and ``pit [...]`` = ``rank_code / (2K)``.
+
+    A row that holds a NaN (or whose target is NaN) gets NaN quantiles / crps / pit and ``rank_code`` -1.  Every output of a row depends on
+    that row alone; nothing synchronises with the host."""
+    _need_gpu(samples, "samples")
+    if samples.dim() < 1 or samples.shape[-1] < 1:
+        raise ValueError(f"samples must be [...,K] with K >= 1, got {tuple(samples.shape)}")
+    lead, K = tuple(samples.shape[:-1]), samples.shape[-1]
+    x = _f32c(samples).reshape(-1, K)
+    M, dev = x.shape[0], x.device
+    y = None
+    if target is not None:
+        if tuple(target.shape) != lead:
+            raise ValueError(f"target must be {lead} (samples without the last axis), got {tuple(target.shape)}")
+        y = _f32c(target).to(dev).reshape(-1)
+    lv = [] if levels is None else L.quantile_levels(levels, K)
+    if len(lv) > 16:
+        raise ValueError(f"at most 16 quantile levels per launch, got {len(lv)}")
+    if not lv and y is None and not return_sorted:
+        raise ValueError("k_scores: nothing to compute - give levels=, target= or return_sorted=True")
+    out = {}
+    if lv:
+        out["quantiles"] = torch.empty(M, len(lv), device=dev)
+    if return_sorted:
+        out["sorted"] = torch.empty(M, K, device=dev)
+    if y is not None:
+        out["crps"], out["pit"] = torch.empty(M, device=dev), torch.empty(M, device=dev)
+        out["rank_code"] = torch.empty(M, dtype=torch.int32, device=dev)
+    if M > 0:
+        L.k_scores(x, M, K, target=y, sorted_out=out.get("sorted"), quantiles=out.get("quantiles"), levels=lv, rank_code=out.get("rank_code"),
+                   pit=out.get("pit"), crps=out.get("crps"))
+    return {k: v.reshape(lead + tuple(v.shape[1:])) for k, v in out.items()}
+
+
 def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True, raw=False, weights=False, pts=False, kstats=False,
                 entropy=True):
     """cfnerf_render_fwd of the packed ``rays [N,11]`` into newly allocated outputs.  Returns a dict with ``rgb_map [N,3,K]``,

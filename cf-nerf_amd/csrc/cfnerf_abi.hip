@@ -158,7 +158,7 @@ static int check_device(const cfnerf_model* m) {
 // CFNERF_F_SEAM_GRAD belongs to the white_bkgd argument of cfnerf_composite_bwd alone, CFNERF_F_CULL turns the pts argument of
 // cfnerf_sample_points into a host cfnerf_cull (and travels in the white_bkgd argument of cfnerf_composite_fwd), CFNERF_F_EPS_GRAD asks the
 // backward of a cfnerf_render_fwd / cfnerf_network_fwd stash for d loss / d eps, CFNERF_F_RAY_REG belongs to the white_bkgd argument of
-// cfnerf_composite_fwd alone (the ray regularisers of a cfnerf_ray_reg).
+// cfnerf_composite_fwd alone (the ray regularisers of a cfnerf_ray_reg), and so does CFNERF_F_KSCORES (the ensemble scores of a cfnerf_kscores).
 // Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
@@ -179,6 +179,8 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_EPS_GRAD (the latent gradient of cfnerf_render_fwd / cfnerf_network_fwd with CFNERF_F_STASH, written by their backward)", who);
     if (flags & CFNERF_F_RAY_REG)                       // (no entry point with a `flags` argument takes it)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_RAY_REG (the ray regularisers of cfnerf_composite_fwd, passed in its white_bkgd argument)", who);
+    if (flags & CFNERF_F_KSCORES)                       // (no entry point with a `flags` argument takes it)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_KSCORES (the ensemble scores of cfnerf_composite_fwd, passed in its white_bkgd argument)", who);
     return CFNERF_OK;
 }
 
@@ -236,6 +238,49 @@ static int composite_ray_reg(const float* raw, const float* z_vals, const float*
     a.cd = (float)((double)rr->lambda_dist * a.inv); a.ce = (float)((double)rr->lambda_ent * a.inv);
     a.lambda_dist = rr->lambda_dist; a.lambda_ent = rr->lambda_ent; a.acc_min = rr->acc_min;
     HIPCHK(launch_ray_reg(a, st));
+    return CFNERF_OK;
+}
+
+// CFNERF_F_KSCORES in the white_bkgd argument of cfnerf_composite_fwd: everything is checked by name before anything touches a device
+static int composite_kscores(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K, int white_bkgd, const float* rgb_map,
+                             const float* disp_map, const float* depth_map, const cfnerf_kscores* ks, hipStream_t st) {
+    if (white_bkgd & CFNERF_F_CULL)
+        return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES cannot be combined with CFNERF_F_CULL (nothing is composited: the rows of samples [N,K] are scored)");
+    if (white_bkgd & CFNERF_F_RAY_REG)
+        return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES cannot be combined with CFNERF_F_RAY_REG (each selects a mode of its own, with its own struct in weights_opt)");
+    if (!ks) return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: the weights_opt argument must be (float*)&ks of a host struct cfnerf_kscores, got NULL");
+    const struct { const void* p; const char* name; } banned[] = {{raw, "raw"}, {z_vals, "z_vals"}, {rays_d, "rays_d"}, {rgb_map, "rgb_map"},
+                                                                  {disp_map, "disp_map"}, {depth_map, "depth_map"}};
+    for (const auto& b : banned)
+        if (b.p) return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: the %s argument must be NULL (nothing is composited)", b.name);
+    if (!ks->samples) return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: member samples of cfnerf_kscores is NULL");
+    if (!ks->sorted && !ks->quantiles && !ks->rank_code && !ks->pit && !ks->crps)
+        return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: no output requested (sorted, quantiles, rank_code, pit and crps of cfnerf_kscores are all NULL)");
+    const struct { const void* p; const char* name; } scored[] = {{ks->crps, "crps"}, {ks->pit, "pit"}, {ks->rank_code, "rank_code"}};
+    for (const auto& o : scored)
+        if (o.p && !ks->target) return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: member %s of cfnerf_kscores needs member target, which is NULL", o.name);
+    if (S != 1) return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: S must be 1 (the rows are samples [N,K]), got %d", S);
+    if (K < 1) return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: K must be at least 1, got %d", K);
+    if (K > kMaxK) return fail(CFNERF_E_UNSUPPORTED, "CFNERF_F_KSCORES: K must be at most %d, got %d", kMaxK, K);
+    if (N < 0) return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: N must not be negative, got %lld", (long long)N);
+    KScoresArgs a{};
+    if (ks->quantiles) {
+        if (ks->n_levels < 1 || ks->n_levels > 16)
+            return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: member n_levels of cfnerf_kscores must be in [1,16] with quantiles, got %d", ks->n_levels);
+        for (int t = 0; t < ks->n_levels; ++t) {
+            if (ks->level_lo[t] < 0 || ks->level_lo[t] > K - 1)
+                return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: member level_lo[%d] of cfnerf_kscores is %d, outside [0, K-1] = [0, %d]", t, ks->level_lo[t], K - 1);
+            if (!(ks->level_frac[t] >= 0.f && ks->level_frac[t] < 1.f))
+                return fail(CFNERF_E_INVALID, "CFNERF_F_KSCORES: member level_frac[%d] of cfnerf_kscores is %g, outside [0, 1)", t, (double)ks->level_frac[t]);
+            a.level_lo[t] = ks->level_lo[t];
+            a.level_frac[t] = ks->level_frac[t];
+        }
+        a.Q = ks->n_levels;
+    }
+    a.samples = ks->samples; a.target = ks->target; a.sorted = ks->sorted; a.quantiles = ks->quantiles;
+    a.rank_code = ks->rank_code; a.pit = ks->pit; a.crps = ks->crps;
+    a.M = N; a.K = K;
+    HIPCHK(launch_k_scores(a, st));
     return CFNERF_OK;
 }
 
@@ -516,6 +561,9 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
 int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K,
                          int white_bkgd, float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
                          cfnerf_stream s) {
+    if (white_bkgd & CFNERF_F_KSCORES)           // nothing is composited: weights_opt is a host cfnerf_kscores, N rows of K samples
+        return composite_kscores(raw, z_vals, rays_d, N, S, K, white_bkgd, rgb_map, disp_map, depth_map,
+                                 reinterpret_cast<const cfnerf_kscores*>(weights_opt), (hipStream_t)s);
     if (white_bkgd & CFNERF_F_RAY_REG)           // nothing is composited: weights_opt is a host cfnerf_ray_reg
         return composite_ray_reg(raw, z_vals, rays_d, N, S, K, white_bkgd, rgb_map, disp_map, depth_map,
                                  reinterpret_cast<const cfnerf_ray_reg*>(weights_opt), (hipStream_t)s);

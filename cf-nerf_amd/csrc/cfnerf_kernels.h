@@ -99,6 +99,18 @@ struct RayRegArgs {
     double inv;                     // 1 / (n_total K)
 };
 hipError_t launch_ray_reg(const RayRegArgs& a, hipStream_t st);      // zeroes the accumulators, then one launch
+// CFNERF_F_KSCORES (cfnerf_kscores.hip): the K samples of each row of samples [M,K] sorted and scored as an ensemble, from a cfnerf_kscores
+struct KScoresArgs {
+    const float *samples, *target;  // [M,K]; [M] or null
+    float *sorted, *quantiles;      // [M,K] or null; [M,Q] or null
+    int32_t* rank_code;             // [M] or null
+    float *pit, *crps;              // [M] or null
+    int64_t M;
+    int32_t K, Q;
+    int32_t level_lo[16];           // quantile level t: x_(lo) + frac (x_(min(lo+1, K-1)) - x_(lo))
+    float level_frac[16];
+};
+hipError_t launch_k_scores(const KScoresArgs& a, hipStream_t st);    // one launch (none when M = 0)
 hipError_t launch_pack_index(const PackDesc* descs, int ndesc, uint32_t total, uint32_t* table /*[total][3]*/, hipStream_t st);      // once per model
 hipError_t launch_pack(const float* flat, float* packed, void* packed16, const uint32_t* table, uint32_t total, hipStream_t st);
 

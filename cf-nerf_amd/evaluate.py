@@ -10,6 +10,9 @@ uncertainty maps of RUN:1117-1131, sparsification_plot HLP:382-438).
 * ``render_uncertainty(stats="ext")`` / ``image_metrics``: the four numbers of the paper's tables (PSNR, NLL, AUSE of the colour and of
   the depth uncertainty) from ONE launch per image (CFNERF_F_KSTATS_EXT: 48 + 24 B per pixel, + 12 B of ground truth, no per-K map),
   with ``sparsification_curves`` / ``ause_fused`` as the device-side form of the reference's sparsification helper.
+* ``render_uncertainty(scores=levels)`` / ``calibration`` / ``image_metrics(calibration=True)``: the K samples of a pixel scored as an ENSEMBLE
+  (CFNERF_F_KSCORES, ``api.k_scores``) - quantile maps (median colour and depth, credible intervals), the CRPS, the rank of the truth among
+  the samples and, from the ranks, the coverage of the central intervals and the area under the calibration error.
 * ``render_uncertainty(stats="geometry")`` / ``density_grid``: depth and disparity maps with their uncertainty, and density /
   density-uncertainty volumes, from launches that skip the colour branch (CFNERF_F_GEOMETRY).
 """
@@ -22,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, render, render_rays_culled, t_vals_table, warp_probe_chunk, warp_z_vals
+from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, k_scores, render, render_rays_culled, t_vals_table, warp_probe_chunk, warp_z_vals
 
 
 def render_path_train(render_poses, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0):
@@ -124,9 +127,26 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
     ``occupancy=`` an ``OccupancySampler`` (``grid.sampler()``; ``stats="basic"`` only) SAMPLES through the grid on the fused path instead:
     per ray chunk ``api.warp_z_vals`` places all S depths inside the occupied part of the ray and one explicit-depth fused launch writes
     the ``[n,8]`` statistics (no per-K map leaves the chip unless ``want_maps``; nothing synchronises).  Adds ``occupied_bins``, the mean of
-    ``n_occ / bins`` over the rays (a device scalar)."""
+    ``n_occ / bins`` over the rays (a device scalar).
+
+    ``scores=levels`` (keyword; a sequence of at most 16 quantile levels in [0,1]; ``stats="basic"`` or ``"ext"``) also scores the K samples of every
+    pixel as an ensemble (``api.k_scores``, CFNERF_F_KSCORES): ``rgb_q [h,W,3,Q]`` and ``depth_q [h,W,Q]``, the quantile maps (level 0.5: the
+    median colour and the median depth); with ``gt`` also ``rgb_crps``, ``rgb_pit [h,W,3]`` and ``rgb_rank [h,W,3]`` (int32), with
+    ``gt_depth [h,W]`` ``depth_crps``, ``depth_pit`` and ``depth_rank [h,W]`` (``calibration`` turns the ranks into coverage figures).  The
+    rows are walked in chunks of ``_SCORES_RAY_CHUNK`` rays: a chunk is one fused forward that also writes its per-K maps, then the scoring
+    launch on ``rgb_map`` and ``depth_map``; the maps of a chunk are dropped before the next one, so no whole-image per-K map exists unless
+    ``want_maps`` asks for it.  Every key the call returns without ``scores=`` keeps its bits (rays are independent).  One combination pays
+    a second forward per chunk: ``stats="ext"`` with ``gt`` and without ``want_maps``, where ``nll`` is the fused kernel's own
+    (cfnerf_render_eval) and the per-K maps come from a maps-only launch.  Refused with ``stats="geometry"`` and with ``occupancy=``."""
     if stats not in ("basic", "ext", "geometry"):
         raise ValueError(f"stats must be 'basic', 'ext' or 'geometry', got {stats!r}")
+    # (keyword-only, taken from the catch-all: tests/test_cull_cpu.py pins the named parameters of this function)
+    scores, gt_depth = _ignored.get("scores"), _ignored.get("gt_depth")
+    if scores is not None and (occupancy is not None or stats == "geometry"):
+        raise ValueError("scores= is not supported with occupancy= or stats='geometry' (it scores the per-K maps of the plain fused forward, "
+                         "stats='basic' or 'ext')")
+    if gt_depth is not None and scores is None:
+        raise ValueError("gt_depth= is the target of the depth scores: it needs scores=levels")
     if occupancy is not None:
         if stats != "basic":
             raise ValueError(f"occupancy= supports stats='basic' only, got {stats!r}: the culled path ends in the standalone composite, which has "
@@ -150,6 +170,8 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
     net._sync()
     eps = net.eval_eps()
     flags = (L.F_LINDISP if lindisp else 0) | (L.F_WHITE_BKGD if white_bkgd else 0) | (L.F_KSTATS_EXT if ext else 0)
+    if scores is not None:
+        return _render_uncertainty_scored(net, packed, t_vals, eps, flags, ext, r1 - r0, W, want_maps, gt, gt_depth, scores)
     sq = nll = None
     if want_maps:
         o = _render_fwd(net, packed, t_vals, None, eps, flags, kstats=True, entropy=False)
@@ -177,6 +199,74 @@ def render_uncertainty(H, W, focal, c2w, network_fn, near=0., far=1., ndc=True, 
                    acc_unc=kst[:, 11].reshape(h, W))
         if sq is not None and nll is None:
             sq, nll = sq[:, 0:3].contiguous(), sq[:, 3:6]           # (sq_err contiguous: ``mse`` then reduces exactly as in "basic")
+    if sq is not None:
+        out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
+    if nll is not None:
+        out.update(nll=nll.reshape(h, W, 3), loss_nll=nll.mean())
+    return out
+
+
+_SCORES_RAY_CHUNK = 1 << 14    # rays per forward + scoring round of render_uncertainty(scores=): bounds the per-K maps (20 K bytes per ray)
+
+
+def _render_uncertainty_scored(net, packed, t_vals, eps, flags, ext, h, W, want_maps, gt, gt_depth, levels):
+    """``render_uncertainty(scores=levels)``: the rays in chunks of ``_SCORES_RAY_CHUNK``; per chunk the fused forward with its per-K maps, then
+    ``k_scores`` on ``rgb_map`` and ``depth_map``.  The keys of the call without ``scores=`` are produced the way that call produces them."""
+    dev = net.device
+    n, K, S = packed.shape[0], net.K_samples, t_vals.shape[0]
+    levels = list(levels)
+    Q = len(levels)
+    L.quantile_levels(levels, K)                                  # (refuses a level outside [0,1] before anything is rendered)
+    if not 1 <= Q <= 16:
+        raise ValueError(f"scores= takes 1 to 16 quantile levels, got {Q}")
+    g = None if gt is None else gt.to(dev, torch.float32).reshape(n, 3).contiguous()
+    gd = None if gt_depth is None else gt_depth.to(dev, torch.float32).reshape(n).contiguous()
+    fused_nll = ext and g is not None and not want_maps          # nll is then the fused kernel's own: statistics from cfnerf_render_eval
+    kst = torch.empty(n, 12 if ext else 8, device=dev)
+    sqn = torch.empty(n, 6, device=dev) if fused_nll else None
+    maps = [torch.empty(n, 3, K, device=dev), torch.empty(n, K, device=dev), torch.empty(n, K, device=dev)] if want_maps else None
+    out = dict(rgb_q=torch.empty(n, 3, Q, device=dev), depth_q=torch.empty(n, Q, device=dev))
+    if g is not None:
+        out.update(rgb_crps=torch.empty(n, 3, device=dev), rgb_pit=torch.empty(n, 3, device=dev), rgb_rank=torch.empty(n, 3, dtype=torch.int32, device=dev))
+    if gd is not None:
+        out.update(depth_crps=torch.empty(n, device=dev), depth_pit=torch.empty(n, device=dev), depth_rank=torch.empty(n, dtype=torch.int32, device=dev))
+    for i in range(0, n, _SCORES_RAY_CHUNK):
+        j = min(n, i + _SCORES_RAY_CHUNK)
+        rays = packed[i:j]
+        if fused_nll:
+            L.check(L.lib().cfnerf_render_eval(net.handle, L.ptr(rays), L.ptr(t_vals), L.ptr(eps), j - i, S, K, flags, L.ptr(g[i:j]), L.ptr(kst[i:j]),
+                                               L.ptr(sqn[i:j]), L.stream()), "cfnerf_render_eval")
+            o = _render_fwd(net, rays, t_vals, None, eps, flags & ~L.F_KSTATS_EXT, entropy=False)
+        else:
+            o = _render_fwd(net, rays, t_vals, None, eps, flags, kstats=True, entropy=False)
+            kst[i:j] = o['kstats']
+        if want_maps:
+            maps[0][i:j], maps[1][i:j], maps[2][i:j] = o['rgb_map'], o['disp_map'], o['depth_map']
+        c = k_scores(o['rgb_map'], target=None if g is None else g[i:j], levels=levels)
+        d = k_scores(o['depth_map'], target=None if gd is None else gd[i:j], levels=levels)
+        out['rgb_q'][i:j], out['depth_q'][i:j] = c['quantiles'], d['quantiles']
+        if g is not None:
+            out['rgb_crps'][i:j], out['rgb_pit'][i:j], out['rgb_rank'][i:j] = c['crps'], c['pit'], c['rank_code']
+        if gd is not None:
+            out['depth_crps'][i:j], out['depth_pit'][i:j], out['depth_rank'][i:j] = d['crps'], d['pit'], d['rank_code']
+        del o, c, d
+    out = {k: v.reshape((h, W) + tuple(v.shape[1:])) for k, v in out.items()}
+    # the keys of the call without scores=, assembled as render_uncertainty assembles them
+    sq = nll = None
+    if g is not None:
+        if fused_nll:
+            sq, nll = sqn[:, 0:3].contiguous(), sqn[:, 3:6]
+        else:
+            sq = (kst[:, 0:3] - g) ** 2
+            if ext:
+                nll = kde_nll(maps[0], g)
+    out.update(rgb_mean=kst[:, 0:3].reshape(h, W, 3), rgb_unc=kst[:, 3:6].reshape(h, W, 3), disp_mean=kst[:, 6].reshape(h, W),
+               depth_mean=kst[:, 7].reshape(h, W))
+    if want_maps:
+        out.update(rgb_map=maps[0].reshape(h, W, 3, K), disp_map=maps[1].reshape(h, W, K), depth_map=maps[2].reshape(h, W, K))
+    if ext:
+        out.update(disp_unc=kst[:, 8].reshape(h, W), depth_unc=kst[:, 9].reshape(h, W), acc_mean=kst[:, 10].reshape(h, W),
+                   acc_unc=kst[:, 11].reshape(h, W))
     if sq is not None:
         out.update(sq_err=sq.reshape(h, W, 3), mse=sq.mean())
     if nll is not None:
@@ -471,8 +561,70 @@ def ause_fused(var_vec, err_vec, err_type='rmse'):
     return float(np.mean(v - o))
 
 
+def _central_inside(levels, K):
+    """For each central level p (a fraction a/b, b <= 1000) the 2K+1 flags ``b |code - K| <= a K`` over code = 0..2K, and ``ideal``: the same
+    rule over the K+1 equally likely values of #below of a calibrated ensemble (code = 2 #below)."""
+    from fractions import Fraction
+    codes, below = np.arange(2 * K + 1), 2 * np.arange(K + 1)
+    inside, ideal = [], []
+    for p in levels:
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f"a central level must lie in [0, 1], got {p!r}")
+        f = Fraction(float(p)).limit_denominator(1000)
+        a, b = f.numerator, f.denominator
+        inside.append(b * np.abs(codes - K) <= a * K)
+        ideal.append(float(np.count_nonzero(b * np.abs(below - K) <= a * K)) / (K + 1))
+    return np.stack(inside), np.asarray(ideal)
+
+
 @torch.no_grad()
-def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, **render_kw):
+def calibration(rank_code, K, levels=(0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9), group=None, n_groups=None):
+    """Calibration of a K-member ensemble from the ranks of the truth among its samples: ``rank_code`` (any shape, integer) as
+    ``api.k_scores`` / ``render_uncertainty(scores=)`` give it, ``2 #{x_k < y} + #{x_k == y}`` in [0, 2K], -1 = not scored (a NaN).
+    One ``bincount`` on the device and one copy of its 2K+2 integers (per group) to the host.  Returns a dict of host values:
+
+    * ``pit_hist [2K+1]`` (int64): how many rows have each code; ``n`` their number, ``n_invalid`` the rows with code -1 (left out);
+    * ``coverage [len(levels)]``: the share of rows whose truth lies inside the central interval of level p.  Defined from the rank, in
+      integers, so it is exact: with p = j/10 a row is inside iff ``10 |rank_code - K| <= j K`` (in general p = a/b: ``b |rank_code - K| <= a K``);
+    * ``ideal``: the coverage a perfectly calibrated K-member ensemble shows under that rule - the truth is exchangeable with the samples,
+      so #below is uniform on 0..K: ``ideal_j = #{b in 0..K : 10 |2b - K| <= j K} / (K + 1)`` (not p itself: K + 1 ranks are a coarse grid);
+    * ``auce`` = ``mean_j |coverage_j - ideal_j|``, the area under the calibration error (nan without a valid row).
+
+    ``group`` (an integer tensor of the shape of ``rank_code``, values 0..G-1, e.g. the channel) gives every result a leading ``[G]`` axis (``n_groups`` = G saves the copy of ``group.max()``)."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"K must be at least 1, got {K}")
+    code = rank_code.reshape(-1).to(torch.int64)
+    width = 2 * K + 2
+    G = 1
+    idx = code + 1
+    if group is not None:
+        if tuple(group.shape) != tuple(rank_code.shape):
+            raise ValueError(f"group must have the shape of rank_code {tuple(rank_code.shape)}, got {tuple(group.shape)}")
+        grp = group.reshape(-1).to(code.device, torch.int64)
+        G = int(n_groups) if n_groups is not None else (int(grp.max().item()) + 1 if grp.numel() else 1)
+        idx = idx + grp * width
+    counts = torch.bincount(idx, minlength=G * width)
+    if counts.numel() != G * width:
+        raise ValueError(f"rank_code must lie in [-1, 2K] = [-1, {2 * K}] (and group in [0, {G - 1}])")
+    counts = counts.cpu().numpy().astype(np.int64).reshape(G, width)
+    inside, ideal = _central_inside(levels, K)
+    hist, n_invalid = counts[:, 1:], counts[:, 0]
+    n = hist.sum(1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        coverage = (hist[:, None, :] * inside[None]).sum(-1) / n[:, None].astype(np.float64)
+    auce = np.abs(coverage - ideal[None]).mean(1)
+    ideal_g = np.broadcast_to(ideal, coverage.shape).copy()
+    if group is None:
+        return dict(pit_hist=hist[0], coverage=coverage[0], ideal=ideal_g[0], auce=float(auce[0]), n=int(n[0]), n_invalid=int(n_invalid[0]))
+    return dict(pit_hist=hist, coverage=coverage, ideal=ideal_g, auce=auce, n=n, n_invalid=n_invalid)
+
+
+_calibration = calibration      # (image_metrics has an argument of that name)
+
+
+@torch.no_grad()
+def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, calibration=False, **render_kw):
     """The per-view numbers of the paper's tables for the image seen from ``c2w`` against ``gt [H,W,3]`` (and ``gt_depth [H,W]``): one
     ``render_uncertainty(stats="ext", gt=gt)`` launch - no per-K map exists anywhere - plus the sorts of ``ause_fused``.  Returns floats:
 
@@ -482,11 +634,19 @@ def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, **render_kw):
     * with ``gt_depth``: ``ause_depth_rmse`` / ``ause_depth_mae`` from ``depth_mean`` and ``depth_unc ** 2`` likewise.
 
     All AUSE figures use ``uncert_type='v'`` like ``ause`` (the most uncertain pixels are removed first; the reference's ``'c'`` keeps
-    them, HLP:414-416,424).  ``render_kw``: near, far, ndc, lindisp, white_bkgd, t_vals of ``render_uncertainty``."""
-    for k in ("rows", "want_maps", "stats", "gt"):
+    them, HLP:414-416,424).  ``render_kw``: near, far, ndc, lindisp, white_bkgd, t_vals of ``render_uncertainty``.
+
+    ``calibration=True`` also scores the K samples of every pixel as an ensemble (``render_uncertainty(scores=)``: the rows are walked in
+    chunks, each with a second, maps-only forward): ``crps_rgb`` (the mean CRPS over pixels and channels), ``auce_rgb`` and ``coverage_rgb``
+    (a list: the coverage of the central 10 % .. 90 % intervals, see ``calibration``); with ``gt_depth`` also ``crps_depth``, ``auce_depth``
+    and ``coverage_depth``.  With the default the returned dict is what it was."""
+    for k in ("rows", "want_maps", "stats", "gt", "scores"):
         if k in render_kw:
             raise TypeError(f"image_metrics renders the whole image with stats='ext' and its own gt: {k}= is not an argument")
-    r = render_uncertainty(H, W, focal, c2w, network_fn, gt=gt, stats="ext", **render_kw)
+    if calibration:
+        r = render_uncertainty(H, W, focal, c2w, network_fn, gt=gt, stats="ext", scores=(0.5,), gt_depth=gt_depth, **render_kw)
+    else:
+        r = render_uncertainty(H, W, focal, c2w, network_fn, gt=gt, stats="ext", **render_kw)
     mse = r["mse"]
     out = dict(mse=float(mse), psnr=float(-10. * torch.log(mse) / math.log(10.)), loss_nll=float(r["loss_nll"]))
     var = (r["rgb_unc"] ** 2).mean(-1).reshape(-1)
@@ -498,4 +658,11 @@ def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, **render_kw):
         var = (r["depth_unc"] ** 2).reshape(-1)
         out["ause_depth_rmse"] = ause_fused(var, (d * d).reshape(-1), 'rmse')
         out["ause_depth_mae"] = ause_fused(var, d.abs().reshape(-1), 'mae')
+    if calibration:
+        K = _unwrap(network_fn).K_samples
+        for what in ("rgb",) + (("depth",) if gt_depth is not None else ()):
+            c = _calibration(r[what + "_rank"], K)
+            out["crps_" + what] = float(r[what + "_crps"].mean())
+            out["auce_" + what] = c["auce"]
+            out["coverage_" + what] = [float(v) for v in c["coverage"]]
     return out

@@ -197,7 +197,7 @@ enum {
                                            cfnerf_render_bwd_accumulate.  No atomics: bit-reproducible.  cfnerf_workspace_bytes does not change - the
                                            caller's grad_flat is the only new memory.  Every other entry point that takes flags refuses it.  Without the
                                            flag there is no extra launch and every argument, buffer shape and output bit is what it was */
-    CFNERF_F_RAY_REG    = 0x2000        /* (= 1 << 13, bit 13) the two ray regularisers of few-view training as ONE stateless launch over the composite's
+    CFNERF_F_RAY_REG    = 0x2000,       /* (= 1 << 13, bit 13) the two ray regularisers of few-view training as ONE stateless launch over the composite's
                                            weights [N,S,K] (what CFNERF_F_COTANGENTS made differentiable): the distortion loss of mip-NeRF 360 and the
                                            ray-entropy loss of InfoNeRF, with their gradient.  There is no new entry point: the bit is or-ed into the
                                            `white_bkgd` ARGUMENT of cfnerf_composite_fwd, which then composites nothing - z_vals [N,S] (non-decreasing
@@ -223,6 +223,34 @@ enum {
                                            cfnerf_composite_bwd does not take the bit; every entry point that takes `flags` refuses it.  NOTE: a white_bkgd
                                            value with bit 13 set used to mean "white" like any non-zero value; it now selects this mode (nothing in the
                                            project passes such a value).  Without the bit every call is what it was */
+    CFNERF_F_KSCORES    = 0x4000        /* (= 1 << 14, bit 14) the K latent samples of a pixel scored as an ENSEMBLE, as ONE stateless launch over the
+                                           rows of samples [M,K] (rgb_map [N,3,K] as M = 3N rows, depth_map / disp_map [N,K] as M = N rows): each row
+                                           sorted ascending, its quantiles and - against a target y - the rank of y among the samples (the PIT) and the
+                                           CRPS of the ensemble.  There is no new entry point: the bit is or-ed into the `white_bkgd` ARGUMENT of
+                                           cfnerf_composite_fwd, which then composites nothing - N is the number of rows M, S must be 1, K in [1, 128],
+                                           raw, z_vals, rays_d, rgb_map, disp_map and depth_map must be NULL, and the `weights_opt` ARGUMENT is read as a
+                                           pointer to a HOST struct cfnerf_kscores (below), (float*)&ks; the struct is read during the call and not
+                                           kept.  Every output is optional, at least one must be requested.  For one row x_0 .. x_K-1 with order
+                                           statistics x_(0) <= .. <= x_(K-1) (NaN orders after +inf, as torch.sort does):
+                                             sorted     the row ascending: a permutation of its 32-bit patterns (compare-and-select, no arithmetic on a
+                                                        value: denormals, +-0, +-inf pass through untouched)
+                                             quantiles  level t of n_levels <= 16 is (level_lo[t], level_frac[t]), made by the HOST from q in [0,1]:
+                                                        lo = floor(q (K-1)) in double, frac = the fractional part rounded once to float; the value is
+                                                        x_(lo) + frac (x_(hi) - x_(lo)), hi = min(lo + 1, K - 1) - numpy.quantile(method="linear"); with
+                                                        frac == 0 it is x_(lo) bit for bit
+                                             rank_code  (int32) 2 #{x_k < y} + #{x_k == y}, in [0, 2K];  pit = (float)rank_code / (float)(2K)
+                                             crps       A - B,  A = (1/K) sum_k |x_k - y|,  B = (1/K^2) sum_{g<K-1} (g+1)(K-1-g) (x_(g+1) - x_(g)): B is the
+                                                        ensemble's 1/(2K^2) sum_kl |x_k - x_l| over the sorted gaps, non-negative terms only
+                                           rank_code, pit and crps need target [M].  A row that holds a NaN, or whose target is NaN, gets NaN quantiles /
+                                           crps / pit and rank_code -1; the other rows are not affected.  No atomics and no reduction across rows: every
+                                           output of a row depends on that row alone - bit-reproducible, whatever rows share a launch.  Refused by name,
+                                           before anything touches a device: a NULL struct, a NULL samples, no output requested, crps / pit / rank_code
+                                           without target, quantiles with n_levels outside [1,16], a level_lo outside [0, K-1] or a level_frac outside
+                                           [0,1), a non-NULL raw / z_vals / rays_d / rgb_map / disp_map / depth_map, S != 1, K < 1, K > 128, N < 0, the
+                                           bit together with CFNERF_F_CULL or CFNERF_F_RAY_REG.  cfnerf_composite_bwd does not take the bit; every entry
+                                           point that takes `flags` refuses it.  NOTE: a white_bkgd value with bit 14 set used to mean "white" like any
+                                           non-zero value; it now selects this mode (nothing in the project passes such a value).  Without the bit every
+                                           call is what it was */
 };
 
 /* The cotangents of a CFNERF_F_COTANGENTS backward: a HOST struct of DEVICE pointers, passed in place of d_rgb_map. */
@@ -278,6 +306,21 @@ typedef struct cfnerf_ray_reg {
     float*  scalars_out;                /* 8 floats out, 8-byte aligned, required: {reg, dist, ent, frac, 0, 0, 0, 0}; the 32 bytes serve as the
                                            launch's accumulators until it ends */
 } cfnerf_ray_reg;
+
+/* The inputs and outputs of a CFNERF_F_KSCORES cfnerf_composite_fwd: a HOST struct of DEVICE pointers and host quantile levels, passed in
+ * place of weights_opt; read during the call, not kept. */
+typedef struct cfnerf_kscores {
+    const float* samples;               /* [M,K] required, row-major */
+    const float* target;                /* [M] or NULL; required by rank_code, pit and crps */
+    float*   sorted;                    /* [M,K] out or NULL */
+    float*   quantiles;                 /* [M,n_levels] out or NULL */
+    int32_t* rank_code;                 /* [M] out or NULL: 2 #below + #equal; -1 for a row with a NaN */
+    float*   pit;                       /* [M] out or NULL: rank_code / (2K) */
+    float*   crps;                      /* [M] out or NULL */
+    int32_t  n_levels;                  /* quantile levels, 1..16 (read with quantiles only) */
+    int32_t  level_lo[16];              /* floor(q (K-1)), in [0, K-1] */
+    float    level_frac[16];            /* q (K-1) - level_lo, in [0, 1) */
+} cfnerf_kscores;
 
 CFNERF_API int         cfnerf_version(void);
 CFNERF_API const char* cfnerf_last_error(void);
@@ -407,7 +450,9 @@ CFNERF_API int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* 
  * read; a ray's rows are fetched through a descriptor of exactly its block [ray_start[ray], ray_start[ray + 1]), so inconsistent indices
  * read zeros, never another ray's rows.  A NULL struct, slot or ray_start is refused.  No backward: cfnerf_composite_bwd does not take the bit.
  * With CFNERF_F_RAY_REG or-ed into white_bkgd nothing is composited: the call evaluates the distortion and ray-entropy regularisers of
- * weights [N,S,K] and their gradient, from (float*)&rr of a host struct cfnerf_ray_reg in weights_opt (contract at the flag). */
+ * weights [N,S,K] and their gradient, from (float*)&rr of a host struct cfnerf_ray_reg in weights_opt (contract at the flag).
+ * With CFNERF_F_KSCORES or-ed into white_bkgd nothing is composited either: the call sorts and scores the N rows of samples [N,K] as
+ * ensembles (quantiles, PIT rank, CRPS), from (float*)&ks of a host struct cfnerf_kscores in weights_opt (contract at the flag). */
 CFNERF_API int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d,
                          int64_t N, int S, int K, int white_bkgd,
                          float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
