@@ -161,6 +161,60 @@ def k_scores(samples, M, K, target=None, sorted_out=None, quantiles=None, levels
                                      stream() if stream_ is None else stream_), "cfnerf_composite_fwd(CFNERF_F_KSCORES)")
 
 
+# CFNERF_MODE_SSIM (enum cfnerf_mode; or-ed into the white_bkgd argument of cfnerf_composite_fwd: weights_opt is an SSim)
+MODE_SSIM = 0x8000
+SSIM_TILE = 32              # CFNERF_SSIM_TILE
+
+
+class SSim(C.Structure):
+    """cfnerf_ssim of include/cfnerf.h: the inputs and outputs of a CFNERF_MODE_SSIM cfnerf_composite_fwd, passed in place of weights_opt
+    (``struct_arg``)"""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("ssim_map", C.c_void_p), ("mean", C.c_void_p), ("scratch", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("win", C.c_int32), ("cov_norm", C.c_double), ("c1", C.c_double), ("c2", C.c_double),
+                ("taps", C.c_float * 15)]
+
+
+def ssim_scratch_floats(B, C_, H, W, win):
+    """CFNERF_SSIM_SCRATCH_FLOATS of include/cfnerf.h: the floats of SSim.scratch (two per 32 x 32 tile, image and channel)"""
+    return 2 * B * C_ * ((H - win) // SSIM_TILE + 1) * ((W - win) // SSIM_TILE + 1)
+
+
+def ssim_window(kind="uniform", win=None, sigma=1.5):
+    """``(taps, cov_norm)`` of a CFNERF_MODE_SSIM window, the taps as Python floats that are exact fp32 values.  ``"uniform"``: ``win``
+    (default 7) equal taps and the sample covariance ``n / (n - 1)``, ``n = win ** 2`` - skimage's default.  ``"gaussian"``: ``exp(-i^2 / (2
+    sigma^2))`` on ``-r .. r``, normalised in double and rounded once to fp32, ``cov_norm = 1`` - ``gaussian_weights=True``; ``win`` defaults
+    to ``2 int(3.5 sigma + 0.5) + 1`` (11 at sigma = 1.5)."""
+    import math
+    import struct
+    if kind not in ("uniform", "gaussian"):
+        raise ValueError(f"window must be 'uniform' or 'gaussian', got {kind!r}")
+    if kind == "gaussian" and not sigma > 0:
+        raise ValueError(f"sigma must be positive, got {sigma!r}")
+    if win is None:
+        win = 7 if kind == "uniform" else 2 * int(3.5 * sigma + 0.5) + 1
+    win = int(win)
+    if win % 2 == 0 or not 3 <= win <= 15:
+        raise ValueError(f"the window must have an odd number of taps in [3, 15], got {win}")
+    if kind == "uniform":
+        taps, cov = [1.0 / win] * win, win * win / (win * win - 1.0)
+    else:
+        r = (win - 1) // 2
+        w = [math.exp(-0.5 / (sigma * sigma) * i ** 2) for i in range(-r, r + 1)]
+        tot = math.fsum(w)
+        taps, cov = [v / tot for v in w], 1.0
+    return [struct.unpack("f", struct.pack("f", t))[0] for t in taps], cov
+
+
+def ssim(x, y, B, H, W, C_, taps, cov_norm, c1, c2, ssim_map=None, mean=None, scratch=None, stream_=None):
+    """One CFNERF_MODE_SSIM call on contiguous fp32 device tensors x, y [B,H,W,C]: writes the outputs that are given (ssim_map
+    [B,H-win+1,W-win+1,C], mean [B,C]); ``scratch``: ``ssim_scratch_floats`` floats, needed with mean.  Nothing synchronises."""
+    s = SSim(dptr(x), dptr(y), dptr(ssim_map), dptr(mean), dptr(scratch), H, W, len(taps), cov_norm, c1, c2)
+    for i, t in enumerate(taps[:15]):
+        s.taps[i] = t
+    check(lib().cfnerf_composite_fwd(None, None, None, B, 1, C_, MODE_SSIM, None, None, None, struct_arg(s),
+                                     stream() if stream_ is None else stream_), "cfnerf_composite_fwd(CFNERF_MODE_SSIM)")
+
+
 def struct_arg(st):
     """the host address of a descriptor struct, as the pointer argument it replaces"""
     return C.cast(C.pointer(st), C.c_void_p)

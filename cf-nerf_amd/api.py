@@ -1028,6 +1028,48 @@ def k_scores(samples, target=None, levels=None, return_sorted=False):
     return {k: v.reshape(lead + tuple(v.shape[1:])) for k, v in out.items()}
 
 
+@torch.no_grad()
+def ssim(img, gt, data_range=1.0, window="uniform", win_size=None, sigma=1.5, full=False):
+    """The structural similarity of ``img`` and ``gt`` - ``[H,W]``, ``[H,W,C]`` or ``[B,H,W,C]`` fp32 tensors on the GPU, C <= 4 - as
+    ``skimage.metrics.structural_similarity(img, gt, data_range=data_range, channel_axis=-1)`` computes it, in ONE call of the fused kernel
+    (CFNERF_MODE_SSIM, include/cfnerf.h has the definitions): ``window="uniform"`` is skimage's default (7 x 7 box, sample covariance),
+    ``window="gaussian"`` its ``gaussian_weights=True`` (sigma = 1.5: 11 x 11); ``win_size`` overrides the number of taps (odd, 3..15).
+    Returns the mean over the valid interior and the channels, one value per image (a 0-dim tensor without a batch axis); with
+    ``full=True`` also the map on the interior, ``[..., H-win+1, W-win+1(, C)]`` - there is no boundary mode, where skimage's full map
+    carries a border that its own mean crops.  The window moments are accumulated in fp64, so a bright, flat render does not lose its
+    variance against C2 as ``E[x^2] - mu^2`` does in fp32.  Nothing synchronises with the host."""
+    _need_gpu(img, "img")
+    _need_gpu(gt, "gt")
+    if tuple(img.shape) != tuple(gt.shape):
+        raise ValueError(f"img and gt must have one shape, got {tuple(img.shape)} and {tuple(gt.shape)}")
+    if img.dim() not in (2, 3, 4):
+        raise ValueError(f"img must be [H,W], [H,W,C] or [B,H,W,C], got {tuple(img.shape)}")
+    if not data_range > 0:
+        raise ValueError(f"data_range must be positive, got {data_range!r}")
+    taps, cov = L.ssim_window(window, win_size, sigma)
+    win = len(taps)
+    x, y = _f32c(img), _f32c(gt)
+    shape = {2: (1,) + tuple(x.shape) + (1,), 3: (1,) + tuple(x.shape), 4: tuple(x.shape)}[x.dim()]
+    B, H, W, C_ = shape
+    if not 1 <= C_ <= 4:
+        raise ValueError(f"at most 4 channels (channel-last), got {C_}")
+    if H < win or W < win:
+        raise ValueError(f"the image ({H} x {W}) is smaller than the window ({win} taps): the valid interior is empty")
+    dev = x.device
+    mean = torch.empty(B, C_, device=dev)
+    smap = torch.empty(B, H - win + 1, W - win + 1, C_, device=dev) if full else None
+    if B > 0:
+        scratch = torch.empty(L.ssim_scratch_floats(B, C_, H, W, win) // 2, dtype=torch.float64, device=dev)
+        L.ssim(x, y, B, H, W, C_, taps, cov, (0.01 * data_range) ** 2, (0.03 * data_range) ** 2, ssim_map=smap, mean=mean, scratch=scratch)
+    value = mean.double().mean(-1).float()
+    if img.dim() < 4:
+        value = value[0]
+    if not full:
+        return value
+    return value, smap.reshape(tuple(img.shape[:-2]) + (H - win + 1, W - win + 1) if img.dim() == 2 else
+                               tuple(img.shape[:-3]) + (H - win + 1, W - win + 1, C_))
+
+
 def _render_fwd(model, rays, t_vals, t_rand, eps, flags, z_vals=None, maps=True, raw=False, weights=False, pts=False, kstats=False,
                 entropy=True):
     """cfnerf_render_fwd of the packed ``rays [N,11]`` into newly allocated outputs.  Returns a dict with ``rgb_map [N,3,K]``,

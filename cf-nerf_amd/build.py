@@ -11,7 +11,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libcfnerf_hip.so")
 CONSUMER = os.path.join(OBJ, "abi_consumer")
 HOOKS = os.path.join(OBJ, "libcfnerf_testhooks.so")        # TEST artefact (tests/cfnerf_debug.h); the product never loads it
-SOURCES = ["cfnerf_fwd.hip", "cfnerf_bwd.hip", "cfnerf_tail.hip", "cfnerf_inputgrad.hip", "cfnerf_raygrad.hip", "cfnerf_cull.hip", "cfnerf_abi.hip", "cfnerf_rayreg.hip", "cfnerf_kscores.hip"]
+SOURCES = ["cfnerf_fwd.hip", "cfnerf_bwd.hip", "cfnerf_tail.hip", "cfnerf_inputgrad.hip", "cfnerf_raygrad.hip", "cfnerf_cull.hip", "cfnerf_abi.hip", "cfnerf_rayreg.hip", "cfnerf_kscores.hip", "cfnerf_ssim.hip"]
 # per-file flags: the flow-adjoint kernels are long straight-line scalar code that the SLP vectoriser makes slower (cfnerf_tail.hip)
 EXTRA_FLAGS = {"cfnerf_tail.hip": ["-fno-slp-vectorize"]}
 # -ffp-contract=off: the sampling / encoding arithmetic must round like the reference's separate

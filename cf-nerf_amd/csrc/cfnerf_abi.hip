@@ -1,6 +1,7 @@
 // cfnerf_abi.hip - the extern "C" boundary of libcfnerf_hip.so (see include/cfnerf.h).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -158,7 +159,8 @@ static int check_device(const cfnerf_model* m) {
 // CFNERF_F_SEAM_GRAD belongs to the white_bkgd argument of cfnerf_composite_bwd alone, CFNERF_F_CULL turns the pts argument of
 // cfnerf_sample_points into a host cfnerf_cull (and travels in the white_bkgd argument of cfnerf_composite_fwd), CFNERF_F_EPS_GRAD asks the
 // backward of a cfnerf_render_fwd / cfnerf_network_fwd stash for d loss / d eps, CFNERF_F_RAY_REG belongs to the white_bkgd argument of
-// cfnerf_composite_fwd alone (the ray regularisers of a cfnerf_ray_reg), and so does CFNERF_F_KSCORES (the ensemble scores of a cfnerf_kscores).
+// cfnerf_composite_fwd alone (the ray regularisers of a cfnerf_ray_reg), and so do CFNERF_F_KSCORES (the ensemble scores of a cfnerf_kscores)
+// and CFNERF_MODE_SSIM (the image similarity of a cfnerf_ssim; an enum of its own, the same argument).
 // Anywhere else they would be silently ignored: `allowed` holds those of them that `who` takes.
 static int refuse_mode_flags(int flags, int allowed, const char* who) {
     if (flags & CFNERF_F_KSTATS_EXT & ~allowed)
@@ -181,6 +183,8 @@ static int refuse_mode_flags(int flags, int allowed, const char* who) {
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_RAY_REG (the ray regularisers of cfnerf_composite_fwd, passed in its white_bkgd argument)", who);
     if (flags & CFNERF_F_KSCORES)                       // (no entry point with a `flags` argument takes it)
         return fail(CFNERF_E_INVALID, "%s does not take CFNERF_F_KSCORES (the ensemble scores of cfnerf_composite_fwd, passed in its white_bkgd argument)", who);
+    if (flags & CFNERF_MODE_SSIM)                       // (no entry point with a `flags` argument takes it)
+        return fail(CFNERF_E_INVALID, "%s does not take CFNERF_MODE_SSIM (the image similarity of cfnerf_composite_fwd, passed in its white_bkgd argument)", who);
     return CFNERF_OK;
 }
 
@@ -281,6 +285,56 @@ static int composite_kscores(const float* raw, const float* z_vals, const float*
     a.rank_code = ks->rank_code; a.pit = ks->pit; a.crps = ks->crps;
     a.M = N; a.K = K;
     HIPCHK(launch_k_scores(a, st));
+    return CFNERF_OK;
+}
+
+// CFNERF_MODE_SSIM in the white_bkgd argument of cfnerf_composite_fwd: everything is checked by name before anything touches a device
+static int composite_ssim(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K, int white_bkgd, const float* rgb_map,
+                          const float* disp_map, const float* depth_map, const cfnerf_ssim* ss, hipStream_t st) {
+    const struct { int bit; const char* name; } modes[] = {{CFNERF_F_CULL, "CFNERF_F_CULL"}, {CFNERF_F_RAY_REG, "CFNERF_F_RAY_REG"},
+                                                           {CFNERF_F_KSCORES, "CFNERF_F_KSCORES"}};
+    for (const auto& o : modes)
+        if (white_bkgd & o.bit)
+            return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM cannot be combined with %s (each selects a mode of its own, with its own struct in weights_opt)", o.name);
+    if (!ss) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: the weights_opt argument must be (float*)&s of a host struct cfnerf_ssim, got NULL");
+    const struct { const void* p; const char* name; } banned[] = {{raw, "raw"}, {z_vals, "z_vals"}, {rays_d, "rays_d"}, {rgb_map, "rgb_map"},
+                                                                  {disp_map, "disp_map"}, {depth_map, "depth_map"}};
+    for (const auto& b : banned)
+        if (b.p) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: the %s argument must be NULL (nothing is composited)", b.name);
+    if (!ss->x) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member x of cfnerf_ssim is NULL");
+    if (!ss->y) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member y of cfnerf_ssim is NULL");
+    if (!ss->ssim_map && !ss->mean) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: no output requested (ssim_map and mean of cfnerf_ssim are both NULL)");
+    if (ss->mean && !ss->scratch) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member mean of cfnerf_ssim needs member scratch, which is NULL");
+    if (ss->mean && reinterpret_cast<uintptr_t>(ss->scratch) % 8)
+        return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member scratch of cfnerf_ssim must be 8-byte aligned (it holds doubles)");
+    if (S != 1) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: S must be 1 (N images of K channels), got %d", S);
+    if (K < 1 || K > 4) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: K (the channel count) must be in [1,4], got %d", K);
+    if (N < 0) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: N must not be negative, got %lld", (long long)N);
+    const int win = ss->win;
+    if (win < 3 || win > kSsimMaxWin || win % 2 == 0)
+        return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member win of cfnerf_ssim must be odd and in [3,%d], got %d", kSsimMaxWin, win);
+    if (ss->H < win) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member H of cfnerf_ssim is %d, below win = %d (the valid interior is empty)", ss->H, win);
+    if (ss->W < win) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member W of cfnerf_ssim is %d, below win = %d (the valid interior is empty)", ss->W, win);
+    const struct { double v; const char* name; } positive[] = {{ss->cov_norm, "cov_norm"}, {ss->c1, "c1"}, {ss->c2, "c2"}};
+    for (const auto& q : positive)
+        if (!(q.v > 0.) || !std::isfinite(q.v))
+            return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member %s of cfnerf_ssim must be finite and positive, got %g", q.name, q.v);
+    SsimArgs a{};
+    double tsum = 0.;
+    for (int i = 0; i < win; ++i) {
+        if (!std::isfinite(ss->taps[i])) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member taps[%d] of cfnerf_ssim is not finite", i);
+        tsum += (double)ss->taps[i];
+    }
+    if (!(tsum > 0.)) return fail(CFNERF_E_INVALID, "CFNERF_MODE_SSIM: member taps of cfnerf_ssim must sum to a positive number, got %g", tsum);
+    for (int i = 0; i < win; ++i) a.taps[i] = (double)ss->taps[i] / tsum;
+    a.tiles_y = (ss->H - win) / kSsimTile + 1; a.tiles_x = (ss->W - win) / kSsimTile + 1;
+    if ((double)N * K * a.tiles_y * a.tiles_x > 2147483647.)
+        return fail(CFNERF_E_UNSUPPORTED, "CFNERF_MODE_SSIM: N * K * tiles = %lld * %d * %d * %d workgroups, above 2^31 - 1: split the batch", (long long)N, K, a.tiles_y, a.tiles_x);
+    a.x = ss->x; a.y = ss->y; a.map = ss->ssim_map; a.mean = ss->mean;
+    a.partials = ss->mean ? reinterpret_cast<double*>(ss->scratch) : nullptr;
+    a.B = N; a.C = K; a.H = ss->H; a.W = ss->W; a.win = win;
+    a.cov_norm = ss->cov_norm; a.c1 = ss->c1; a.c2 = ss->c2;
+    HIPCHK(launch_ssim(a, st));
     return CFNERF_OK;
 }
 
@@ -561,6 +615,9 @@ int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* eps, int64_
 int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d, int64_t N, int S, int K,
                          int white_bkgd, float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
                          cfnerf_stream s) {
+    if (white_bkgd & CFNERF_MODE_SSIM)           // nothing is composited: weights_opt is a host cfnerf_ssim, N image pairs of K channels
+        return composite_ssim(raw, z_vals, rays_d, N, S, K, white_bkgd, rgb_map, disp_map, depth_map,
+                              reinterpret_cast<const cfnerf_ssim*>(weights_opt), (hipStream_t)s);
     if (white_bkgd & CFNERF_F_KSCORES)           // nothing is composited: weights_opt is a host cfnerf_kscores, N rows of K samples
         return composite_kscores(raw, z_vals, rays_d, N, S, K, white_bkgd, rgb_map, disp_map, depth_map,
                                  reinterpret_cast<const cfnerf_kscores*>(weights_opt), (hipStream_t)s);

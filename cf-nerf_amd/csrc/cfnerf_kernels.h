@@ -111,6 +111,20 @@ struct KScoresArgs {
     float level_frac[16];
 };
 hipError_t launch_k_scores(const KScoresArgs& a, hipStream_t st);    // one launch (none when M = 0)
+// CFNERF_MODE_SSIM (cfnerf_ssim.hip): the SSIM map and per-image means of two image batches [B,H,W,C], from a cfnerf_ssim
+constexpr int kSsimTile = 32;       // output tile of one workgroup (CFNERF_SSIM_TILE of include/cfnerf.h)
+constexpr int kSsimMaxWin = 15;
+struct SsimArgs {
+    const float *x, *y;             // [B,H,W,C]
+    float* map;                     // [B,H-win+1,W-win+1,C] or null
+    float* mean;                    // [B,C] or null
+    double* partials;               // [B,C,tiles_y,tiles_x] tile sums (the caller's scratch); null without mean
+    int64_t B;
+    int32_t C, H, W, win, tiles_y, tiles_x;
+    double cov_norm, c1, c2;
+    double taps[kSsimMaxWin];       // the struct's fp32 taps divided by their sum, in double
+};
+hipError_t launch_ssim(const SsimArgs& a, hipStream_t st);           // the map / tile-sum launch, then the mean's (none when B = 0)
 hipError_t launch_pack_index(const PackDesc* descs, int ndesc, uint32_t total, uint32_t* table /*[total][3]*/, hipStream_t st);      // once per model
 hipError_t launch_pack(const float* flat, float* packed, void* packed16, const uint32_t* table, uint32_t total, hipStream_t st);
 

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib as L
 from .api import _network_geometry, _pack_rays, _render_fwd, _unwrap, k_scores, render, render_rays_culled, t_vals_table, warp_probe_chunk, warp_z_vals
+from .api import ssim as _ssim      # (image_metrics has an argument of that name)
 
 
 def render_path_train(render_poses, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0):
@@ -624,7 +625,7 @@ _calibration = calibration      # (image_metrics has an argument of that name)
 
 
 @torch.no_grad()
-def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, calibration=False, **render_kw):
+def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, calibration=False, ssim=False, **render_kw):
     """The per-view numbers of the paper's tables for the image seen from ``c2w`` against ``gt [H,W,3]`` (and ``gt_depth [H,W]``): one
     ``render_uncertainty(stats="ext", gt=gt)`` launch - no per-K map exists anywhere - plus the sorts of ``ause_fused``.  Returns floats:
 
@@ -639,7 +640,11 @@ def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, calibration=F
     ``calibration=True`` also scores the K samples of every pixel as an ensemble (``render_uncertainty(scores=)``: the rows are walked in
     chunks, each with a second, maps-only forward): ``crps_rgb`` (the mean CRPS over pixels and channels), ``auce_rgb`` and ``coverage_rgb``
     (a list: the coverage of the central 10 % .. 90 % intervals, see ``calibration``); with ``gt_depth`` also ``crps_depth``, ``auce_depth``
-    and ``coverage_depth``.  With the default the returned dict is what it was."""
+    and ``coverage_depth``.  With the default the returned dict is what it was.
+
+    ``ssim=True`` adds ``ssim`` (skimage's default: 7 x 7 uniform window, ``data_range=1``) and ``ssim_gaussian`` (Wang et al.: 11 x 11,
+    sigma = 1.5) of the K-mean image that the one launch already returns against ``gt`` (``cfnerf_amd.ssim``): no second render.  With the
+    default the returned dict is what it was."""
     for k in ("rows", "want_maps", "stats", "gt", "scores"):
         if k in render_kw:
             raise TypeError(f"image_metrics renders the whole image with stats='ext' and its own gt: {k}= is not an argument")
@@ -665,4 +670,8 @@ def image_metrics(H, W, focal, c2w, network_fn, gt, gt_depth=None, calibration=F
             out["crps_" + what] = float(r[what + "_crps"].mean())
             out["auce_" + what] = c["auce"]
             out["coverage_" + what] = [float(v) for v in c["coverage"]]
+    if ssim:
+        img, ref = r["rgb_mean"], gt.to(sq.device, torch.float32).reshape(H, W, 3)
+        out["ssim"] = float(_ssim(img, ref))
+        out["ssim_gaussian"] = float(_ssim(img, ref, window="gaussian"))
     return out

@@ -253,6 +253,42 @@ enum {
                                            call is what it was */
 };
 
+/* A mode bit that is not a flag of the network: like CFNERF_F_RAY_REG and CFNERF_F_KSCORES it travels in the `white_bkgd` ARGUMENT of
+ * cfnerf_composite_fwd and selects a stateless launch of its own, but it has an enum of its own.
+ *
+ * CFNERF_MODE_SSIM (bit 15): the structural similarity (Wang et al. 2004; skimage.metrics.structural_similarity) of two image batches
+ * x, y [B,H,W,C] - channel-last fp32, as the evaluation renders are - under a separable odd window of `win` taps, on the VALID interior:
+ * with p = (win - 1) / 2 the map is [B,H-2p,W-2p,C] (there is no boundary mode), and `mean` [B,C] is its mean per image and channel.  With
+ * the bit set nothing is composited: N is the number of images B, S must be 1, K is the channel count C in [1,4], raw, z_vals, rays_d,
+ * rgb_map, disp_map and depth_map must be NULL, and the `weights_opt` ARGUMENT is read as a pointer to a HOST struct cfnerf_ssim (below),
+ * (float*)&s; the struct is read during the call and not kept.  For every interior pixel and channel, with the taps t (used as t_i / sum t):
+ *     mu_x, mu_y = sum_ij t_i t_j x, y          v_x, v_y, v_xy = cov_norm (sum_ij t_i t_j x^2, y^2, xy  -  mu_x^2, mu_y^2, mu_x mu_y)
+ *     S = (2 mu_x mu_y + c1)(2 v_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(v_x + v_y + c2))
+ * One kernel serves both conventions, because the HOST supplies taps and cov_norm: skimage's default is the uniform window, win = 7,
+ * cov_norm = n / (n - 1) with n = win^2; gaussian_weights=True (Wang et al.) is sigma = 1.5, radius int(3.5 sigma + 0.5) = 5, win = 11,
+ * cov_norm = 1, the taps normalised in double and rounded once to float.  c1 = (0.01 L)^2 and c2 = (0.03 L)^2 for a data range L.
+ * Arithmetic: the five window moments are accumulated in fp64 from the fp32 pixels (x^2 is then exact), so v = E[x^2] - mu^2 does not
+ * cancel against c2 on a bright, flat image as it does in fp32; the quotient is rounded once to fp32.  ssim(x, x) is exactly 1.0f at every
+ * pixel and in the mean.  Every output pixel depends on the win x win pixels under its window alone: a NaN pixel makes NaN exactly the
+ * outputs whose window covers it, plus mean[b,c] of its image and channel.  The mean is the sum of the fp32 map values, in fp64 and in a
+ * fixed order (one partial sum per 32 x 32 tile in `scratch`, added by a second small launch): no atomics, bit-reproducible, and nothing
+ * of an image depends on its batch-mates.  ssim_map and mean are each optional, at least one must be requested; mean needs scratch:
+ * CFNERF_SSIM_SCRATCH_FLOATS(B, C, H, W, win) floats, 8-byte aligned (it holds doubles), owned by the caller, free once the stream has
+ * passed the call.  Refused by name, before anything touches a device: a NULL struct, a NULL x or y, no output requested, mean without
+ * scratch, a misaligned scratch, win even or outside [3,15], H or W below win, K outside [1,4], S != 1, N < 0 (N == 0 is accepted and
+ * launches nothing), more than 2^31 - 1 tiles, a non-finite or non-positive c1, c2 or cov_norm, a non-finite tap or taps that do not
+ * sum to a positive number, a non-NULL raw / z_vals / rays_d / rgb_map / disp_map / depth_map, the bit together with CFNERF_F_CULL,
+ * CFNERF_F_RAY_REG or CFNERF_F_KSCORES.  Every entry point that takes `flags` refuses the bit.  cfnerf_composite_bwd does not take it:
+ * there the background is white iff (white_bkgd & ~CFNERF_F_SEAM_GRAD) != 0, as it was, whatever other bits are set.  NOTE: in
+ * cfnerf_composite_fwd a white_bkgd value with bit 15 set used to mean "white" like any non-zero value; it now selects this mode (nothing
+ * in the project passes such a value).  Without the bit every call is what it was. */
+enum cfnerf_mode { CFNERF_MODE_SSIM = 0x8000 };   /* bit 15 */
+
+#define CFNERF_SSIM_TILE 32             /* the output tile of one workgroup: one partial sum per tile, image and channel */
+/* floats of cfnerf_ssim.scratch for B images of H x W x C under a window of win taps (H, W >= win): two per partial sum */
+#define CFNERF_SSIM_SCRATCH_FLOATS(B, C, H, W, win) \
+    (2 * (int64_t)(B) * (int64_t)(C) * (((H) - (win)) / CFNERF_SSIM_TILE + 1) * (((W) - (win)) / CFNERF_SSIM_TILE + 1))
+
 /* The cotangents of a CFNERF_F_COTANGENTS backward: a HOST struct of DEVICE pointers, passed in place of d_rgb_map. */
 typedef struct cfnerf_cotangents {
     const float* d_rgb_map;             /* [N,3,K]   required */
@@ -321,6 +357,23 @@ typedef struct cfnerf_kscores {
     int32_t  level_lo[16];              /* floor(q (K-1)), in [0, K-1] */
     float    level_frac[16];            /* q (K-1) - level_lo, in [0, 1) */
 } cfnerf_kscores;
+
+/* The inputs and outputs of a CFNERF_MODE_SSIM cfnerf_composite_fwd: a HOST struct of DEVICE pointers and host window parameters, passed
+ * in place of weights_opt; read during the call, not kept. */
+typedef struct cfnerf_ssim {
+    const float* x;                     /* [B,H,W,C] required, channel-last */
+    const float* y;                     /* [B,H,W,C] required */
+    float*   ssim_map;                  /* [B,H-win+1,W-win+1,C] out or NULL */
+    float*   mean;                      /* [B,C] out or NULL; needs scratch */
+    float*   scratch;                   /* CFNERF_SSIM_SCRATCH_FLOATS(B,C,H,W,win) floats, 8-byte aligned, or NULL without mean */
+    int32_t  H;
+    int32_t  W;
+    int32_t  win;                       /* taps of the separable window: odd, 3..15 */
+    double   cov_norm;                  /* n / (n - 1), n = win^2 (sample covariance, skimage's default) or 1 */
+    double   c1;                        /* (0.01 L)^2 */
+    double   c2;                        /* (0.03 L)^2 */
+    float    taps[15];                  /* the first win are read; used as taps[i] / (their sum) */
+} cfnerf_ssim;
 
 CFNERF_API int         cfnerf_version(void);
 CFNERF_API const char* cfnerf_last_error(void);
@@ -452,7 +505,9 @@ CFNERF_API int cfnerf_network_fwd(cfnerf_model* m, const float* x, const float* 
  * With CFNERF_F_RAY_REG or-ed into white_bkgd nothing is composited: the call evaluates the distortion and ray-entropy regularisers of
  * weights [N,S,K] and their gradient, from (float*)&rr of a host struct cfnerf_ray_reg in weights_opt (contract at the flag).
  * With CFNERF_F_KSCORES or-ed into white_bkgd nothing is composited either: the call sorts and scores the N rows of samples [N,K] as
- * ensembles (quantiles, PIT rank, CRPS), from (float*)&ks of a host struct cfnerf_kscores in weights_opt (contract at the flag). */
+ * ensembles (quantiles, PIT rank, CRPS), from (float*)&ks of a host struct cfnerf_kscores in weights_opt (contract at the flag).
+ * With CFNERF_MODE_SSIM or-ed into white_bkgd nothing is composited either: the call writes the SSIM map and the per-image means of the N
+ * image pairs of (float*)&s, a host struct cfnerf_ssim in weights_opt (contract at enum cfnerf_mode). */
 CFNERF_API int cfnerf_composite_fwd(const float* raw, const float* z_vals, const float* rays_d,
                          int64_t N, int S, int K, int white_bkgd,
                          float* rgb_map, float* disp_map, float* depth_map, float* weights_opt,
